@@ -10,7 +10,13 @@ G backward + Adam, D backward + Adam) on one synthetic Cityscapes-shaped batch t
 Default workload = BASELINE.json configs[1] (C2): 512x256 (NCHW (8,.,256,512)), bs 8 per GPU, GlobalGenerator ngf 64 /
 4 downsamples / 9 ResnetBlocks (182.6 M params), 3-scale PatchGAN, VGG19 perceptual loss, fp32 throughout.
 Rank 0 prints ONE JSON line (metric = BASELINE.json's images/s; weak scaling: bs 8 per GPU).  `--workload c2local | c4
-| box2mask` run the other measured configurations under the same protocol (same JSON schema incl. roofline/cpu_baseline).
+| box2mask` run the other measured configurations under the same protocol (same JSON schema).
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, the result line.
+`--full` adds the legs that are measurements of their own: the roofline micro-benchmarks (`roofline`, `g_forward`,
+`step_roofline`) and the CPU oracle (`cpu_baseline`).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float32): its losses, the generated images and a fixed, seeded sample of the updated weights.  Inputs
+and initial weights are seeded, so two builds can be compared output for output with the same arguments.
 """
 import argparse
 import json
@@ -22,6 +28,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -393,11 +400,60 @@ def cpu_baseline(name, wl, timed=3, budget_s=75.0):
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step
+# --------------------------------------------------------------------------------------------------------------------
+DUMP_WEIGHT_SAMPLE = 1 << 20            # entries per network: 4 MB each
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _weight_sample(net, seed):
+    """A fixed, seeded sample of the network's parameters: DUMP_WEIGHT_SAMPLE positions (Philox, sorted) in the
+    concatenation of its parameters in named_parameters() order; all of them when there are fewer."""
+    from neurips18_hierchical_image_manipulation_amd import synth
+    flat = torch.cat([p.detach().reshape(-1) for _, p in net.named_parameters()])
+    if flat.numel() > DUMP_WEIGHT_SAMPLE:
+        idx = np.sort(synth._gen(seed).integers(0, flat.numel(), size=DUMP_WEIGHT_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat
+
+
+def dump_outputs(path, model, losses, outputs):
+    """DIR/<name>.npy, float32: loss_<name> (one value each) and the step's other outputs as the caller receives them
+    (label maps as float), then -- after the optimizer streams are joined -- G_weight_sample / D_weight_sample of the
+    updated weights.  Everything here is seeded (inputs, initial weights, sample positions)."""
+    arrays = {}
+    for k, v in losses.items():
+        arrays['loss_' + k] = (v.detach().reshape(-1).float().cpu().numpy() if torch.is_tensor(v)
+                               else np.array([v], np.float32))
+    for k, v in outputs.items():
+        arrays[k] = v.detach().float().cpu().numpy()
+    if hasattr(model, 'sync'):
+        model.sync()
+    torch.cuda.synchronize()
+    for tag, net, seed in (('G', model.netG, 101), ('D', getattr(model, 'netD', None), 102)):
+        if net is not None:
+            arrays['%s_weight_sample' % tag] = _weight_sample(net, seed).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py --dump-outputs: %d bytes, more than the %d allowed' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
+# --------------------------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline measurement, also run the legs it does not need: the roofline micro-benchmarks '
+                         '("roofline", "g_forward", "step_roofline") and the CPU oracle ("cpu_baseline", rank 0 at N = 1); '
+                         '--no-roofline / --no-cpu-baseline leave one of them out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the LAST timed step computed as DIR/<name>.npy (float32, rank 0): the step's losses, "
+                         'the generated images and a fixed, seeded sample of the updated G / D weights (< 64 MB in all)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--cpu-steps', type=int, default=3, help='timed oracle steps of the cpu_baseline leg')
@@ -449,6 +505,7 @@ def main():
     wl = WORKLOADS[args.workload]
     bs, H, W = wl['bs'], wl['H'], wl['W']
 
+    torch.manual_seed(0)          # whatever the Philox state dicts below do not overwrite is seeded too
     model = create_model(dict(wl['flags'], gpu_ids=[local], isTrain=True, checkpoints_dir='/tmp/him_bench',
                               name='bench_' + args.workload, batchSize=bs))
     # every rank draws the same Philox weights (and attach_data_parallel broadcasts rank 0's state anyway)
@@ -463,11 +520,12 @@ def main():
         batches = [{k: v.to(device) for k, v in synth.make_box2mask_batch(s, rank, bs, H, W).items()} for s in range(4)]
 
         def step(i):
+            """-> (losses, the step's other outputs: train_box2mask.py's [comb_recon_label, obj_recon_label])"""
             b = batches[i % 4]
             names = ['G_Recon_comb', 'G_Recon_obj', 'KL_loss', 'loss_G_GAN', 'loss_D_GAN', 'loss_G_GAN_Feat']
-            out = model.forward(b['label'], None, b['mask_ctx_in'], None, b['mask_out'], b['mask_obj_inst'], b['cls'],
-                                b['mask_in'])[0]
-            return dict(zip(names, out))
+            out, recon = model.forward(b['label'], None, b['mask_ctx_in'], None, b['mask_out'], b['mask_obj_inst'], b['cls'],
+                                       b['mask_in'])
+            return dict(zip(names, out)), dict(comb_recon_label=recon[0], obj_recon_label=recon[1])
     else:
         batches = [{k: v.to(device) for k, v in synth.make_batch(s, rank, bs, H, W, wl['label_nc'], wl['color']).items()}
                    for s in range(4)]
@@ -481,7 +539,8 @@ def main():
             b['ready_event'] = ready
 
         def step(i):
-            return model.optimize_parameters(batches[i % 4])
+            """-> (losses, the step's other outputs: the generated images, which the model keeps for its visuals)"""
+            return model.optimize_parameters(batches[i % 4]), dict(synthesized_image=model._visuals[0])
 
     for i in range(args.warmup):
         step(i)
@@ -494,7 +553,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        losses = step(args.warmup + i)
+        losses, outputs = step(args.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -587,7 +646,9 @@ def main():
                                                                        for e in exposed), 4)}
         if fake is not None:
             out['fake_comm'] = fake
-        if not args.no_roofline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, losses, outputs)
+        if args.full and not args.no_roofline:
             if args.workload == 'box2mask':
                 out['roofline'] = direct_conv_roofline(device, bs, 256, 256, 3, 1, 1, 32, 32,
                                                        'direct fp32-MFMA conv3x3 256->256 @32x32 bs 32 (ResnetBlock latent convs '
@@ -598,7 +659,7 @@ def main():
                 out['g_forward'] = g_forward_roofline(model, batches[0], wl)
                 if args.workload == 'c2':
                     out['step_roofline'] = step_flop_accounting(ms, bs, args.variant)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.workload, wl, args.cpu_steps)
         print(json.dumps(out), flush=True)
     if world > 1:

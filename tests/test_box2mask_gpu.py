@@ -461,7 +461,7 @@ def test_lr_control_predicate_matches_reference_rule():
     assert seen == {(1.0, 1.0), (0.0, 1.0), (1.0, 0.0)}
 
 
-def test_box2mask_evaluation_methods_match_reference_golden():
+def test_box2mask_evaluation_methods_match_reference_golden(tmp_path):
     """generate / reconstruct / evaluate / encode_input and the [comb_recon_label, obj_recon_label] of a training forward
     against the REAL reference's outputs (tests/golden/box2mask_eval.npz, make_golden.py box2mask_eval; same call order:
     generate on fresh running statistics, reconstruct in training mode, evaluate on the moved statistics, one training
@@ -472,7 +472,7 @@ def test_box2mask_evaluation_methods_match_reference_golden():
     from neurips18_hierchical_image_manipulation_amd.models import create_model
     g = load_golden('box2mask_eval')
     fl = json.loads(str(g['flags']))
-    model = create_model(dict(fl, model='AE_maskgen_twostream', gpu_ids=[0], isTrain=True, checkpoints_dir='/tmp/him_b2m',
+    model = create_model(dict(fl, model='AE_maskgen_twostream', gpu_ids=[0], isTrain=True, checkpoints_dir=str(tmp_path),
                               name='t'))
     model.netG.load_state_dict(synth.init_state_dict(model.netG.state_dict(), 21))
     model.netD.load_state_dict(synth.init_state_dict(model.netD.state_dict(), 22))
@@ -525,7 +525,7 @@ def test_box2mask_evaluation_methods_match_reference_golden():
     # checkpoint rotation of train_box2mask.py:138-142: save(epoch) ... delete_model(epoch - num_checkpoint * save_epoch_freq)
     import os
     model.save(7)
-    files = [os.path.join('/tmp/him_b2m', 't', '7_net_%s.pth' % k) for k in 'GD']
+    files = [os.path.join(str(tmp_path), 't', '7_net_%s.pth' % k) for k in 'GD']
     assert all(os.path.isfile(f) for f in files), files
     model.delete_model(7)
     assert not any(os.path.isfile(f) for f in files)
