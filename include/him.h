@@ -200,6 +200,17 @@ int him_batchnorm_bwd(const float* x, const float* gamma, const float* beta, con
 int him_act_fwd(const float* x, float* y, size_t n, int act, float slope, void* stream);
 int him_upsample2_fwd(const float* x, float* y, int planes, int H, int W, int align_corners, void* stream);
 int him_upsample2_bwd(const float* dy, float* dx, int planes, int H, int W, int align_corners, void* stream);
+/* TwoStreamAE_mask.evaluate(target_size) (reference models/TwoStreamAE_mask.py:318-335): the generator's low-resolution
+ * probabilities comb_prob (1,C,h,w) and obj_prob (1,1,h,w) (already gated by the low-resolution mask_out under
+ * --use_output_gate) sampled bilinearly at the (H,W) of the original crop (align_corners as upsample_align_corners,
+ * same source positions as him_upsample2_fwd) and composed with label (1,1,H,W) in one pass; the upsampled C-channel
+ * tensor and the one-hot of the label are never written.
+ *   background 0 (cls != label_nc-1): dst f32 = obj > .5 ? cls : label;           comb_prob / mask_out may be NULL.
+ *   background 1 (cls == label_nc-1): dst i64 = argmax_c (p_c * m + (1 - m) * [label == c]), m = mask_out (1,1,H,W),
+ *                                     the first index wins ties (torch.max(dim)); obj_prob may be NULL. */
+int him_resize_compose(const float* comb_prob, const float* obj_prob, int C, int h, int w, const float* label,
+                       const float* mask_out, int cls, int background, void* dst, int H, int W, int align_corners,
+                       void* stream);
 int him_logsoftmax_fwd(const float* x, float* y, int B, int C, int hw, void* stream);
 int him_logsoftmax_bwd(const float* y, const float* dy, float* dx, int B, int C, int hw, void* stream);
 /* MaskTwoStreamConv_NET.py:213-221 (the generator the parser builds without --no_comb): the context stream's logits gated
@@ -534,6 +545,25 @@ int him_data_bicubic_v(const unsigned char* tmp, int maxrows, const int* first, 
 int him_data_region_masks(const float* label, const void* inst, int inst_kind, const int* boxes, const float* fill,
                           const int* inst_id, float* mask_in, float* obj_in, float* ctx_in, float* mask_out,
                           float* obj_out, float* inst_mask, int B, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Canvas crop / paste of the joint box -> layout -> image edit (reference util/data_util.py crop_canvas / paste_canvas,
+ * models/joint_inference_model.py): the full-resolution canvas stays on the device; the host only supplies windows and
+ * the resampling tables of data/resample.py.  Byte results are bit-identical to ToPILImage -> Pillow 12.2 -> ToTensor.
+ *   him_canvas_window_bytes: dst (h,w,C) interleaved bytes = trunc(pre(src[c][y0+y][x0+x]) * 255) for a window of C
+ *                       fp32 planes (Hs,Ws) that may extend past them (0 there, Image.crop's fill); pre 0: v, 1: v/255,
+ *                       2: (v+1)/2.  C = 1 is the plain 2-D byte map him_data_nearest reads (src_kind 0), C = 3 the
+ *                       interleaved RGB rows him_data_bicubic_h reads.
+ *   him_canvas_paste_bicubic_v: him_data_bicubic_v's column pass of tmp (rows,W,3) without flip / Normalize, written as
+ *                       v/255 into canvas (3,Hc,Wc) at [y0,y0+H) x [x0,x0+W) (the window must lie inside the canvas).
+ *   him_canvas_paste_window: canvas[c][y0+y][x0+x] = src[c][y][x] for C planes (h,w); src_kind 0 f32 / 1 i64.
+ * ------------------------------------------------------------------------------------------- */
+int him_canvas_window_bytes(const float* src, int C, int Hs, int Ws, int x0, int y0, int h, int w, int pre,
+                            unsigned char* dst, void* stream);
+int him_canvas_paste_bicubic_v(const unsigned char* tmp, const int* first, const int* count, const int* weights,
+                               int ksize, float* canvas, int Hc, int Wc, int x0, int y0, int H, int W, void* stream);
+int him_canvas_paste_window(const void* src, int src_kind, int C, int h, int w, float* canvas, int Hc, int Wc, int x0,
+                            int y0, void* stream);
 
 #ifdef __cplusplus
 }

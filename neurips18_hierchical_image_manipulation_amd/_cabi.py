@@ -104,6 +104,7 @@ _SIGS = {
     'him_act_fwd': (c_int, [P, P, c_size_t, c_int, c_float, P]),
     'him_upsample2_fwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     'him_upsample2_bwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    'him_resize_compose': (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, c_int, c_int, P]),
     'him_logsoftmax_fwd': (c_int, [P, P, c_int, c_int, c_int, P]),
     'him_logsoftmax_bwd': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'him_gate_comb_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
@@ -129,6 +130,9 @@ _SIGS = {
     'him_data_bicubic_h': (c_int, [P, P, P, P, P, P, P, c_int, P, c_int, c_int, c_int, P]),
     'him_data_bicubic_v': (c_int, [P, c_int, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     'him_data_region_masks': (c_int, [P, P, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    'him_canvas_window_bytes': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'him_canvas_paste_bicubic_v': (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'him_canvas_paste_window': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

@@ -128,6 +128,65 @@ __global__ void data_region_masks_kernel(const float* __restrict__ label, const 
   }
 }
 
+// ---- canvas crop / paste of the joint inference (util/data_util.py crop_canvas / paste_canvas upstream) ----------
+// ToPILImage of a window of C fp32 planes (Hs, Ws): byte = trunc(pre(v) * 255) with pre 0: v, 1: v / 255 (a label map
+// through tensor2pil), 2: (v + 1) / 2 (the generator's tanh output); each operation rounded on its own, no contraction.
+// Pixels of the window outside the planes are 0 (Image.crop's fill).  dst (h, w, C) interleaved bytes.
+__global__ void canvas_window_bytes_kernel(const float* __restrict__ src, int C, int Hs, int Ws, int x0, int y0, int h,
+                                           int w, int pre, unsigned char* __restrict__ dst) {
+  long long n = (long long)h * w;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int sx = x0 + (int)(i % w), sy = y0 + (int)(i / w);
+    const bool inside = sx >= 0 && sx < Ws && sy >= 0 && sy < Hs;
+    for (int c = 0; c < C; ++c) {
+      unsigned char b = 0;
+      if (inside) {
+        float v = src[((long long)c * Hs + sy) * Ws + sx];
+        if (pre == 1) v = __fdiv_rn(v, 255.f);
+        else if (pre == 2) v = __fdiv_rn(__fadd_rn(v, 1.f), 2.f);
+        b = (unsigned char)(int)__fmul_rn(v, 255.f);   // Tensor.byte(): truncation
+      }
+      dst[i * C + c] = b;
+    }
+  }
+}
+
+// vertical BICUBIC pass of a (rows, W, 3) byte image written as ToTensor (v / 255) into a window of a (3, Hc, Wc) canvas
+__global__ void canvas_paste_bicubic_v_kernel(const unsigned char* __restrict__ tmp, const int* __restrict__ first,
+                                              const int* __restrict__ count, const int* __restrict__ weights, int ksize,
+                                              float* __restrict__ canvas, int Hc, int Wc, int x0, int y0, int W) {
+  const int y = blockIdx.y;
+  const int f = first[y], n = count[y];
+  const int* w = weights + (long long)y * ksize;
+  for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < W; x += gridDim.x * blockDim.x) {
+    int a0 = 1 << (DATA_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+    for (int k = 0; k < n; ++k) {
+      const int wk = w[k];
+      const unsigned char* p = tmp + ((long long)(f + k) * W + x) * 3;
+      a0 += (int)p[0] * wk;
+      a1 += (int)p[1] * wk;
+      a2 += (int)p[2] * wk;
+    }
+    const int v[3] = {clip8(a0), clip8(a1), clip8(a2)};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      canvas[((long long)c * Hc + y0 + y) * Wc + x0 + x] = __fdiv_rn((float)v[c], 255.f);
+  }
+}
+
+// window copy of C planes (h, w) (f32 or i64, converted to f32) into a (C, Hc, Wc) canvas at (x0, y0)
+__global__ void canvas_paste_window_kernel(const void* __restrict__ src, int src_kind, int C, int h, int w,
+                                           float* __restrict__ canvas, int Hc, int Wc, int x0, int y0) {
+  long long n = (long long)C * h * w;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % w);
+    const long long r = i / w;
+    const int y = (int)(r % h), c = (int)(r / h);
+    const float v = src_kind ? (float)((const long long*)src)[i] : ((const float*)src)[i];
+    canvas[((long long)c * Hc + y0 + y) * Wc + x0 + x] = v;
+  }
+}
+
 static inline dim3 data_grid(long long n) {
   long long g = (n + 255) / 256;
   return dim3((unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)));
@@ -185,6 +244,38 @@ int him_data_region_masks(const float* label, const void* inst, int inst_kind, c
   hipLaunchKernelGGL(data_region_masks_kernel, data_grid((long long)B * H * W), dim3(256), 0, ST, label, inst,
                      inst_kind, boxes, fill, inst_id, mask_in, obj_in, ctx_in, mask_out, obj_out, inst_mask, B, H, W);
   return check_launch("data_region_masks");
+}
+
+int him_canvas_window_bytes(const float* src, int C, int Hs, int Ws, int x0, int y0, int h, int w, int pre,
+                            unsigned char* dst, void* stream) {
+  if (C <= 0 || Hs <= 0 || Ws <= 0 || h <= 0 || w <= 0) return fail(HIM_E_INVALID, "canvas_window_bytes: bad shape");
+  if (pre < 0 || pre > 2) return fail(HIM_E_INVALID, "canvas_window_bytes: pre %d", pre);
+  hipLaunchKernelGGL(canvas_window_bytes_kernel, data_grid((long long)h * w), dim3(256), 0, ST, src, C, Hs, Ws, x0, y0, h,
+                     w, pre, dst);
+  return check_launch("canvas_window_bytes");
+}
+
+int him_canvas_paste_bicubic_v(const unsigned char* tmp, const int* first, const int* count, const int* weights,
+                               int ksize, float* canvas, int Hc, int Wc, int x0, int y0, int H, int W, void* stream) {
+  if (H <= 0 || W <= 0 || ksize <= 0 || H > 65535) return fail(HIM_E_INVALID, "canvas_paste_bicubic_v: bad shape");
+  if (x0 < 0 || y0 < 0 || x0 + W > Wc || y0 + H > Hc)
+    return fail(HIM_E_INVALID, "canvas_paste_bicubic_v: window (%d,%d)+(%d,%d) outside the %dx%d canvas", x0, y0, W, H,
+                Wc, Hc);
+  hipLaunchKernelGGL(canvas_paste_bicubic_v_kernel, dim3((W + 255) / 256, H), dim3(256), 0, ST, tmp, first, count,
+                     weights, ksize, canvas, Hc, Wc, x0, y0, W);
+  return check_launch("canvas_paste_bicubic_v");
+}
+
+int him_canvas_paste_window(const void* src, int src_kind, int C, int h, int w, float* canvas, int Hc, int Wc, int x0,
+                            int y0, void* stream) {
+  if (C <= 0 || h <= 0 || w <= 0) return fail(HIM_E_INVALID, "canvas_paste_window: bad shape");
+  if (src_kind < 0 || src_kind > 1) return fail(HIM_E_INVALID, "canvas_paste_window: src_kind %d", src_kind);
+  if (x0 < 0 || y0 < 0 || x0 + w > Wc || y0 + h > Hc)
+    return fail(HIM_E_INVALID, "canvas_paste_window: window (%d,%d)+(%d,%d) outside the %dx%d canvas", x0, y0, w, h, Wc,
+                Hc);
+  hipLaunchKernelGGL(canvas_paste_window_kernel, data_grid((long long)C * h * w), dim3(256), 0, ST, src, src_kind, C, h,
+                     w, canvas, Hc, Wc, x0, y0);
+  return check_launch("canvas_paste_window");
 }
 
 }  // extern "C"

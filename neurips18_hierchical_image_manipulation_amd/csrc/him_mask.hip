@@ -315,6 +315,48 @@ __global__ void upsample2_bwd_kernel(const float* __restrict__ dy, float* __rest
   }
 }
 
+// ---- evaluate(target_size): bilinear resize of the probabilities + composition at the crop's own resolution -------
+// torch's order: h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11), every product and sum rounded on its own
+__device__ __forceinline__ float bilinear_at(const float* __restrict__ p, int w, int y0, int y1, int x0, int x1, float wy,
+                                             float wx) {
+  const float w0 = __fsub_rn(1.f, wx);
+  const float top = __fadd_rn(__fmul_rn(w0, p[y0 * w + x0]), __fmul_rn(wx, p[y0 * w + x1]));
+  const float bot = __fadd_rn(__fmul_rn(w0, p[y1 * w + x0]), __fmul_rn(wx, p[y1 * w + x1]));
+  return __fadd_rn(__fmul_rn(__fsub_rn(1.f, wy), top), __fmul_rn(wy, bot));
+}
+
+// object class:     dst f32 = bilinear(obj) > .5 ? cls : label
+// background class: dst i64 = argmax_c (bilinear(comb_c) * m + (1 - m) * [label == c]), first index wins, NaN wins
+__global__ void resize_compose_kernel(const float* __restrict__ comb, const float* __restrict__ obj, int C, int h, int w,
+                                      const float* __restrict__ label, const float* __restrict__ mask, float cls,
+                                      int background, void* __restrict__ dst, int H, int W, int align) {
+  const long long n = (long long)H * W;
+  GS_LOOP(i, n) {
+    const int ox = (int)(i % W), oy = (int)(i / W);
+    int y0, y1, x0, x1;
+    float wy, wx;
+    bilinear_src(oy, h, H, align, &y0, &y1, &wy);
+    bilinear_src(ox, w, W, align, &x0, &x1, &wx);
+    const float l = label[i];
+    if (!background) {
+      ((float*)dst)[i] = bilinear_at(obj, w, y0, y1, x0, x1, wy, wx) > 0.5f ? cls : l;
+    } else {
+      const float m = mask[i], m1 = __fsub_rn(1.f, m);
+      long long best = 0;
+      float bv = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float p = bilinear_at(comb + (long long)c * h * w, w, y0, y1, x0, x1, wy, wx);
+        const float v = __fadd_rn(__fmul_rn(p, m), __fmul_rn(m1, l == (float)c ? 1.f : 0.f));
+        if (c == 0 || (bv == bv && (v > bv || v != v))) {
+          bv = v;
+          best = c;
+        }
+      }
+      ((long long*)dst)[i] = best;
+    }
+  }
+}
+
 // ---- log-softmax over the channel axis (nn.LogSoftmax(dim=1)) ----------------------------------------------------
 __global__ void logsoftmax_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int C, int hw) {
   const long long n = (long long)B * hw;
@@ -568,6 +610,18 @@ int him_upsample2_bwd(const float* dy, float* dx, int planes, int H, int W, int 
   hipLaunchKernelGGL(upsample2_bwd_kernel, gs_grid((long long)planes * H * W), dim3(256), 0, ST, dy, dx, planes, H, W,
                      align_corners);
   return check_launch("upsample2_bwd");
+}
+
+int him_resize_compose(const float* comb_prob, const float* obj_prob, int C, int h, int w, const float* label,
+                       const float* mask_out, int cls, int background, void* dst, int H, int W, int align_corners,
+                       void* stream) {
+  if (h <= 0 || w <= 0 || H <= 0 || W <= 0 || !label || !dst)
+    return fail(HIM_E_INVALID, "resize_compose: h=%d w=%d H=%d W=%d", h, w, H, W);
+  if (background ? (!comb_prob || !mask_out || C <= 0) : !obj_prob)
+    return fail(HIM_E_INVALID, "resize_compose: missing input for the %s branch", background ? "background" : "object");
+  hipLaunchKernelGGL(resize_compose_kernel, gs_grid((long long)H * W), dim3(256), 0, ST, comb_prob, obj_prob, C, h, w,
+                     label, mask_out, (float)cls, background, dst, H, W, align_corners);
+  return check_launch("resize_compose");
 }
 
 int him_logsoftmax_fwd(const float* x, float* y, int B, int C, int hw, void* stream) {

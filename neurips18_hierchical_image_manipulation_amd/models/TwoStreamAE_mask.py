@@ -40,6 +40,10 @@ def complete(opt):
     return opt
 
 
+class _MissingOrig(KeyError, NotImplementedError):
+    """evaluate(target_size=...) without the original-resolution maps: the reference fails with a KeyError there."""
+
+
 class TwoStreamAE_mask(BaseModel):
     def name(self):
         return 'TwoStreamAE_mask'
@@ -79,6 +83,10 @@ class TwoStreamAE_mask(BaseModel):
                     self.netD = MultiscaleDiscriminator(d_nc, opt.ndf, opt.num_layers_D, opt.norm_layer, False, 2, True)
                 self.netD.to(self.device)
                 self.optimizer_D = FusedAdam(self.netD.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
+        else:
+            # test time (reference :116-118): the generator comes from <checkpoints_dir>/<name>/<which_epoch>_net_G.pth;
+            # a missing file is an error
+            self.load_network_dict(self.params_dict, None, 'G', getattr(opt, 'which_epoch', 'latest'), '')
 
     @property
     def optimizer_G(self):
@@ -289,12 +297,15 @@ class TwoStreamAE_mask(BaseModel):
         return out
 
     def evaluate(self, input_dict, target_size=None):
-        """Reference :303-348 for the first sample of the batch: the label map with the predicted object pasted in (or, for
-        the background class ``label_nc - 1``, the arg-max context map inside the box).  ``target_size`` (bilinear resize
-        of the probabilities to the original resolution) is the visualisation scripts' path and not built."""
+        """Reference :303-335 for the first sample of the batch: the label map with the predicted object pasted in (or, for
+        the background class ``label_nc - 1``, the arg-max context map inside the box).  With ``target_size`` (the joint
+        inference's path) the probabilities are resized bilinearly to the original crop's (H, W) and composed with
+        ``label_map_orig`` / ``mask_out_orig`` instead, in one kernel (ops.resize_compose); ``target_size`` must be that
+        (H, W), as the reference's shapes require."""
         if target_size is not None:
-            raise NotImplementedError('TwoStreamAE_mask.evaluate(target_size=...): arbitrary-size bilinear resampling is '
-                                      'not on the HIP path')
+            for k in ('label_map_orig', 'mask_ctx_in_orig', 'mask_out_orig'):
+                if k not in input_dict:
+                    raise _MissingOrig(k)
         first = lambda k: input_dict[k][0].unsqueeze(0)  # noqa: E731
         label_map, cls = first('label_map'), first('cls')
         was_training = self.netG.training
@@ -309,6 +320,16 @@ class TwoStreamAE_mask(BaseModel):
                 if self.use_output_gate:
                     obj_prob = self.mask_variable(obj_prob, gt_mask)
                 cls_id = int(cls.reshape(-1)[0])
+                if target_size is not None:
+                    # the reference re-encodes the original-resolution maps (mask_in=None); of that only the label map and
+                    # mask_out reach the result, and their one-hot / blend is folded into the kernel
+                    label_orig, mask_out_orig = self._dev(first('label_map_orig')), self._dev(first('mask_out_orig'))
+                    if tuple(int(v) for v in target_size) != tuple(label_orig.shape[2:4]):
+                        raise ValueError('evaluate: target_size %s is not the (H, W) %s of label_map_orig'
+                                         % (tuple(target_size), tuple(label_orig.shape[2:4])))
+                    return ops.resize_compose(comb_prob, obj_prob, label_orig, mask_out_orig, cls_id,
+                                              cls_id == self.opt.label_nc - 1,
+                                              bool(getattr(self.opt, 'upsample_align_corners', False)))
                 if cls_id == self.opt.label_nc - 1:
                     return self.postprocess_output(comb_prob, gt_mask, gt_one_hot).argmax(1, keepdim=True)
                 obj_mask = (obj_prob > 0.5).float()

@@ -2103,3 +2103,137 @@ class _DivScalar(torch.autograd.Function):
 
 def div_scalar(W, sigma):
     return _DivScalar.apply(W, sigma)
+
+
+# -- joint box -> layout -> image edit: evaluate(target_size) and the canvas crop / paste (include/him.h) ---------------
+def resize_compose(comb_prob, obj_prob, label, mask_out, cls, background, align_corners=False):
+    """TwoStreamAE_mask.evaluate(target_size)'s tail (reference :318-335) in one kernel at the (H, W) of ``label``
+    (1,1,H,W): the object class -> fp32 ``obj_prob`` (1,1,h,w) sampled bilinearly > .5 ? cls : label; the background class
+    (``background``) -> int64 arg-max over c of bilinear(comb_prob[c]) * m + (1 - m) * [label == c], m = ``mask_out``."""
+    src = comb_prob if background else obj_prob
+    label = label.contiguous()
+    mask_out = None if mask_out is None else mask_out.contiguous()
+    src = src.contiguous()
+    _chk(src, label, mask_out)
+    if src.dim() != 4 or src.shape[0] != 1 or label.numel() != label.shape[-2] * label.shape[-1]:
+        raise HimError('resize_compose: one sample (1,C,h,w) probabilities and a (1,1,H,W) label map')
+    _, C, h, w = src.shape
+    H, W = label.shape[-2:]
+    if background and (mask_out is None or tuple(mask_out.shape) != tuple(label.shape)):
+        raise HimError('resize_compose: mask_out %s must have the label map\'s shape %s'
+                       % (None if mask_out is None else tuple(mask_out.shape), tuple(label.shape)))
+    other = obj_prob if background else comb_prob
+    if other is not None and tuple(other.shape[-2:]) != (h, w):
+        raise HimError('resize_compose: comb_prob %s and obj_prob %s differ in (h, w)'
+                       % (tuple(comb_prob.shape), tuple(obj_prob.shape)))
+    dst = torch.empty((1, 1, H, W), dtype=torch.int64 if background else torch.float32, device=label.device)
+    lib.him_resize_compose(_p(src) if background else 0, 0 if background else _p(src), C, h, w, _p(label),
+                           _p(mask_out) if background else 0, int(cls), 1 if background else 0, _p(dst), H, W,
+                           1 if align_corners else 0, _stream())
+    return dst
+
+
+def _align16(n):
+    return n + ((-n) % 16)
+
+
+def _scratch_and_tables(lead, arrays, dev):
+    """One device byte buffer: ``lead`` bytes of scratch, then the host ``arrays`` (resampling tables) uploaded with one
+    asynchronous copy from pinned memory on the current stream -> (buffer, device address of each array)."""
+    import numpy as np
+    start = _align16(int(lead))
+    at, size = [], start
+    for a in arrays:
+        at.append(size)
+        size = _align16(size + a.nbytes)
+    host = torch.empty(max(size - start, 16), dtype=torch.uint8, pin_memory=True)
+    view = host.numpy()
+    for o, a in zip(at, arrays):
+        view[o - start:o - start + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    buf = torch.empty(start + host.numel(), dtype=torch.uint8, device=dev)
+    buf[start:].copy_(host, non_blocking=True)
+    base = buf.data_ptr()
+    return buf, [base + o for o in at]
+
+
+def _plane_geometry(t, what):
+    _chk(t)
+    if t.dim() != 4 or t.shape[0] != 1:
+        raise HimError('%s: one (1,C,H,W) fp32 tensor, got %s' % (what, tuple(t.shape)))
+    return t.shape[1], t.shape[2], t.shape[3]
+
+
+def canvas_crop_nearest(canvas, box, H, W, pre=1):
+    """(1,1,H,W) fp32 ids: ToPILImage of the one-channel ``canvas`` (``pre`` 1: the canvas holds ids and is divided by
+    255 first, as tensor2pil does), ``Image.crop(box)`` (integer (x0,y0,x1,y1), may extend past the canvas: zeros),
+    ``resize((W,H), NEAREST)``, ToTensor * 255."""
+    import numpy as np
+    from .data import resample
+    C, Hs, Ws = _plane_geometry(canvas, 'canvas_crop_nearest')
+    if C != 1:
+        raise HimError('canvas_crop_nearest: a label canvas has one channel, got %d' % C)
+    x0, y0, x1, y1 = (int(v) for v in box)
+    w, h = x1 - x0, y1 - y0
+    if w <= 0 or h <= 0:
+        raise HimError('canvas_crop_nearest: empty window %s' % (box,))
+    buf, (o, p, xt, yt) = _scratch_and_tables(h * w, [np.zeros(1, np.int64), np.array([w], np.int32),
+                                                      resample.nearest_table(w, W), resample.nearest_table(h, H)],
+                                              canvas.device)
+    st = _stream()
+    lib.him_canvas_window_bytes(_p(canvas), 1, Hs, Ws, x0, y0, h, w, pre, buf.data_ptr(), st)
+    dst = torch.empty((1, 1, H, W), dtype=torch.float32, device=canvas.device)
+    lib.him_data_nearest(buf.data_ptr(), o, p, xt, yt, 0, _p(dst), 0, 1, H, W, st)
+    return dst
+
+
+def canvas_crop_bicubic(canvas, box, H, W, normalize=True):
+    """(1,3,H,W) fp32: ToPILImage of the RGB ``canvas`` (1,3,Hc,Wc) in [0,1], ``Image.crop(box)`` (zeros outside),
+    ``resize((W,H), BICUBIC)``, ToTensor, optionally Normalize((.5,.5,.5),(.5,.5,.5))."""
+    return _bicubic(canvas, box, H, W, 0, None, (0, 0), normalize)
+
+
+def canvas_paste_bicubic(patch, box, canvas, x0, y0, H, W, pre=0):
+    """In place: the window ``box`` of ``patch`` (1,3,h,w) (inside it) as ToPILImage bytes of pre(v) (0: v, 2: (v+1)/2),
+    ``resize((W,H), BICUBIC)``, ToTensor, written into ``canvas`` (1,3,Hc,Wc) at [y0,y0+H) x [x0,x0+W)."""
+    return _bicubic(patch, box, H, W, pre, canvas, (x0, y0), False)
+
+
+def _bicubic(src, box, H, W, pre, canvas, at, normalize):
+    import numpy as np
+    from .data import resample
+    C, Hs, Ws = _plane_geometry(src, 'canvas bicubic')
+    if C != 3:
+        raise HimError('canvas bicubic: RGB planes, got %d channels' % C)
+    x0, y0, x1, y1 = (int(v) for v in box)
+    w, h = x1 - x0, y1 - y0
+    if w <= 0 or h <= 0 or h > 65535 or H <= 0 or W <= 0:
+        raise HimError('canvas bicubic: bad window %s -> %dx%d' % (box, W, H))
+    fx, nx, wx, ksx = resample.bicubic_tables(w, W)
+    fy, ny, wy, ksy = resample.bicubic_tables(h, H)
+    buf, (o, p, r, afx, anx, awx, afy, any_, awy, fl) = _scratch_and_tables(
+        h * w * 3, [np.zeros(1, np.int64), np.array([w], np.int32), np.array([h], np.int32), fx, nx, wx, fy, ny, wy,
+                    np.zeros(1, np.int32)], src.device)
+    st = _stream()
+    lib.him_canvas_window_bytes(_p(src), 3, Hs, Ws, x0, y0, h, w, pre, buf.data_ptr(), st)
+    tmp = torch.empty((h, W, 3), dtype=torch.uint8, device=src.device)
+    lib.him_data_bicubic_h(buf.data_ptr(), o, p, r, afx, anx, awx, ksx, _p(tmp), h, 1, W, st)
+    if canvas is None:
+        dst = torch.empty((1, 3, H, W), dtype=torch.float32, device=src.device)
+        lib.him_data_bicubic_v(_p(tmp), h, afy, any_, awy, ksy, fl, _p(dst), 1 if normalize else 0, 1, H, W, st)
+        return dst
+    _, Hc, Wc = _plane_geometry(canvas, 'canvas_paste_bicubic')
+    lib.him_canvas_paste_bicubic_v(_p(tmp), afy, any_, awy, ksy, _p(canvas), Hc, Wc, int(at[0]), int(at[1]), H, W, st)
+    return canvas
+
+
+def canvas_paste_window(src, canvas, x0, y0):
+    """In place: canvas[0, :, y0:y0+h, x0:x0+w] = src (1,C,h,w) fp32 or int64 (as fp32)."""
+    src = src.contiguous()
+    if not src.is_cuda or src.dtype not in (torch.float32, torch.int64) or src.dim() != 4 or src.shape[0] != 1:
+        raise HimError('canvas_paste_window: one (1,C,h,w) fp32 / int64 device tensor')
+    C, Hc, Wc = _plane_geometry(canvas, 'canvas_paste_window')
+    if src.shape[1] != C:
+        raise HimError('canvas_paste_window: %d channels into a %d-channel canvas' % (src.shape[1], C))
+    lib.him_canvas_paste_window(_p(src), 1 if src.dtype == torch.int64 else 0, C, src.shape[2], src.shape[3],
+                                _p(canvas), Hc, Wc, int(x0), int(y0), _stream())
+    return canvas
