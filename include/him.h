@@ -565,6 +565,21 @@ int him_canvas_paste_bicubic_v(const unsigned char* tmp, const int* first, const
 int him_canvas_paste_window(const void* src, int src_kind, int C, int h, int w, float* canvas, int Hc, int Wc, int x0,
                             int y0, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tensors to pictures (reference util/util.py tensor2im / tensor2label + Colorize / tensor2seglabel): one pass over a
+ * (C,H,W) device tensor, interleaved bytes out, so that only bytes cross to the host.  No global state; any H, W.
+ *   tensor2im:   src fp32, C = 1 or 3; byte = trunc(clip(normalize ? (x + 1) / 2 * 255 : x * 255, 0, 255)), each
+ *                operation rounded to fp32 on its own (numpy's order); C = 1 writes the value three times.  dst (H,W,3).
+ *   label2color: C > 1: src fp32 scores, label = channel of the maximum, the lowest channel on a tie; C = 1: src holds
+ *                the ids, dtype 0 fp32 / 1 uint8 / 2 int64.  dst (H,W,3) = table[label], table = n rows of 3 bytes on
+ *                the device (n <= 8192).  A label outside [0, n) or a non-integer fp32 id writes (0,0,0).
+ *   seglabel:    src fp32 with values in [0, 255]; dst (H,W,C) = trunc(src).
+ * ------------------------------------------------------------------------------------------- */
+int him_tensor2im_bytes(const float* src, int C, int H, int W, int normalize, unsigned char* dst, void* stream);
+int him_label2color_bytes(const void* src, int dtype, int C, int H, int W, const unsigned char* table, int n,
+                          unsigned char* dst, void* stream);
+int him_seglabel_bytes(const float* src, int C, int H, int W, unsigned char* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

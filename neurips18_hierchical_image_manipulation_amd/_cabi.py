@@ -133,6 +133,9 @@ _SIGS = {
     'him_canvas_window_bytes': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     'him_canvas_paste_bicubic_v': (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'him_canvas_paste_window': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P]),
+    'him_tensor2im_bytes': (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
+    'him_label2color_bytes': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P]),
+    'him_seglabel_bytes': (c_int, [P, c_int, c_int, c_int, P, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

@@ -192,6 +192,168 @@ static inline dim3 data_grid(long long n) {
   return dim3((unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)));
 }
 
+// ---- tensors to pictures (util/util.py tensor2im / tensor2label / tensor2seglabel upstream) ------------------------
+// One pass each, HBM-bound.  A thread owns VIS_PX adjacent pixels of the flattened (H*W) plane: one 16-byte load per
+// channel plane, and the interleaved bytes of its pixels leave as whole dwords (4 RGB pixels = 3 dwords).  `vec` (host:
+// H*W % 4 == 0 and a 16-byte aligned base, so every plane is aligned and every group full) selects the wide loads,
+// `packed` (host: dst 4-byte aligned) the dword stores; otherwise element loads / byte stores, bounds-checked.
+#define VIS_PX 4
+
+template <typename T>
+__device__ __forceinline__ void vis_load4(const T* __restrict__ plane, long long i0, long long n, bool vec, T v[VIS_PX]) {
+  if (vec) {
+    struct alignas(VIS_PX * sizeof(T)) Q { T a[VIS_PX]; };
+    const Q q = *(const Q*)(plane + i0);
+#pragma unroll
+    for (int k = 0; k < VIS_PX; ++k) v[k] = q.a[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < VIS_PX; ++k) v[k] = i0 + k < n ? plane[i0 + k] : T(0);
+  }
+}
+
+// px[k] = r | g << 8 | b << 16 of pixel i0 + k  ->  dst (n, 3) bytes
+__device__ __forceinline__ void vis_store_rgb4(unsigned char* __restrict__ dst, long long i0, long long n, bool packed,
+                                               const unsigned px[VIS_PX]) {
+  if (packed && i0 + VIS_PX <= n) {
+    struct alignas(4) W3 { unsigned a, b, c; };
+    W3 w;
+    w.a = px[0] | (px[1] << 24);
+    w.b = (px[1] >> 8) | (px[2] << 16);
+    w.c = (px[2] >> 16) | (px[3] << 8);
+    *(W3*)(dst + i0 * 3) = w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < VIS_PX; ++k)
+      if (i0 + k < n) {
+        unsigned char* o = dst + (i0 + k) * 3;
+        o[0] = (unsigned char)(px[k] & 255u);
+        o[1] = (unsigned char)((px[k] >> 8) & 255u);
+        o[2] = (unsigned char)(px[k] >> 16);
+      }
+  }
+}
+
+// tensor2im: byte = trunc(clip(normalize ? (x + 1) / 2 * 255 : x * 255, 0, 255)), every operation rounded to fp32 on
+// its own as numpy does (no contraction: the single-FMA form differs in about one value of 1 800)
+__device__ __forceinline__ unsigned im_byte(float x, bool normalize) {
+  float v = normalize ? __fmul_rn(__fmul_rn(__fadd_rn(x, 1.0f), 0.5f), 255.0f) : __fmul_rn(x, 255.0f);
+  v = fminf(fmaxf(v, 0.0f), 255.0f);
+  return (unsigned)(int)v;
+}
+
+__global__ void tensor2im_bytes_kernel(const float* __restrict__ src, int C, long long n, int normalize, int vec,
+                                       int packed, unsigned char* __restrict__ dst) {
+  const long long groups = (n + VIS_PX - 1) / VIS_PX;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i0 = g * VIS_PX;
+    float r[VIS_PX];
+    unsigned px[VIS_PX];
+    vis_load4(src, i0, n, vec != 0, r);
+    if (C == 1) {  // upstream repeats a 1-channel tensor to 3 channels
+#pragma unroll
+      for (int k = 0; k < VIS_PX; ++k) px[k] = im_byte(r[k], normalize != 0) * 0x010101u;
+    } else {
+      float gch[VIS_PX], b[VIS_PX];
+      vis_load4(src + n, i0, n, vec != 0, gch);
+      vis_load4(src + 2 * n, i0, n, vec != 0, b);
+#pragma unroll
+      for (int k = 0; k < VIS_PX; ++k)
+        px[k] = im_byte(r[k], normalize != 0) | (im_byte(gch[k], normalize != 0) << 8) | (im_byte(b[k], normalize != 0) << 16);
+    }
+    vis_store_rgb4(dst, i0, n, packed != 0, px);
+  }
+}
+
+// Colorize's "label == map" on a float map paints integer values in [0, n) only; everything else stays (0, 0, 0)
+__device__ __forceinline__ int vis_label(float v, int n) { return (v >= 0.0f && v < (float)n && v == floorf(v)) ? (int)v : -1; }
+__device__ __forceinline__ int vis_label(unsigned char v, int n) { return (int)v < n ? (int)v : -1; }
+__device__ __forceinline__ int vis_label(long long v, int n) { return (v >= 0 && v < (long long)n) ? (int)v : -1; }
+
+// tensor2label's label branch: C > 1 (T = float): label = channel of the maximum, the LOWEST channel on a tie (strict >
+// walking upwards, what max(0)[1] returns on the host); C == 1: the plane holds the ids.  dst = table[label].
+template <typename T>
+__global__ void label2color_bytes_kernel(const T* __restrict__ src, int C, long long n, const unsigned char* __restrict__ table,
+                                         int ntab, int vec, int packed, unsigned char* __restrict__ dst) {
+  extern __shared__ unsigned vis_tab[];  // ntab entries r | g << 8 | b << 16
+  for (int i = threadIdx.x; i < ntab; i += blockDim.x)
+    vis_tab[i] = (unsigned)table[3 * i] | ((unsigned)table[3 * i + 1] << 8) | ((unsigned)table[3 * i + 2] << 16);
+  __syncthreads();
+  const long long groups = (n + VIS_PX - 1) / VIS_PX;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i0 = g * VIS_PX;
+    int lab[VIS_PX];
+    T v[VIS_PX];
+    vis_load4(src, i0, n, vec != 0, v);
+    if (C == 1) {
+#pragma unroll
+      for (int k = 0; k < VIS_PX; ++k) lab[k] = vis_label(v[k], ntab);
+    } else {
+      T best[VIS_PX];
+#pragma unroll
+      for (int k = 0; k < VIS_PX; ++k) { best[k] = v[k]; lab[k] = 0; }
+#pragma unroll 4
+      for (int c = 1; c < C; ++c) {
+        vis_load4(src + (long long)c * n, i0, n, vec != 0, v);
+#pragma unroll
+        for (int k = 0; k < VIS_PX; ++k)
+          if (v[k] > best[k]) { best[k] = v[k]; lab[k] = c; }
+      }
+#pragma unroll
+      for (int k = 0; k < VIS_PX; ++k) lab[k] = lab[k] < ntab ? lab[k] : -1;
+    }
+    unsigned px[VIS_PX];
+#pragma unroll
+    for (int k = 0; k < VIS_PX; ++k) px[k] = lab[k] >= 0 ? vis_tab[lab[k]] : 0u;
+    vis_store_rgb4(dst, i0, n, packed != 0, px);
+  }
+}
+
+// tensor2seglabel: dst[p][c] = trunc(src[c][p]).  CT = 1..4: the CT * VIS_PX bytes of a thread's pixels leave as CT
+// dwords; CT = 0: any C, byte stores.
+template <int CT>
+__global__ void seglabel_bytes_kernel(const float* __restrict__ src, int C, long long n, int vec, int packed,
+                                      unsigned char* __restrict__ dst) {
+  const long long groups = (n + VIS_PX - 1) / VIS_PX;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i0 = g * VIS_PX;
+    float v[VIS_PX];
+    if constexpr (CT > 0) {
+      unsigned w[CT > 0 ? CT : 1] = {};
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        vis_load4(src + (long long)c * n, i0, n, vec != 0, v);
+#pragma unroll
+        for (int k = 0; k < VIS_PX; ++k) {
+          const int at = k * CT + c;  // byte index inside the thread's CT * VIS_PX output bytes
+          w[at >> 2] |= ((unsigned)(int)v[k] & 255u) << ((at & 3) * 8);
+        }
+      }
+      if (packed && i0 + VIS_PX <= n) {
+#pragma unroll
+        for (int j = 0; j < CT; ++j) ((unsigned*)(dst + i0 * CT))[j] = w[j];
+      } else {
+#pragma unroll
+        for (int at = 0; at < CT * VIS_PX; ++at)
+          if (i0 + at / CT < n) dst[i0 * CT + at] = (unsigned char)(w[at >> 2] >> ((at & 3) * 8));
+      }
+    } else {
+      for (int c = 0; c < C; ++c) {
+        vis_load4(src + (long long)c * n, i0, n, vec != 0, v);
+#pragma unroll
+        for (int k = 0; k < VIS_PX; ++k)
+          if (i0 + k < n) dst[(i0 + k) * C + c] = (unsigned char)(int)v[k];
+      }
+    }
+  }
+}
+
+static inline bool vis_vec(const void* src, long long n, size_t elem) {
+  return n % VIS_PX == 0 && (uintptr_t)src % (VIS_PX * elem) == 0;
+}
+static inline bool vis_packed(const void* dst) { return (uintptr_t)dst % 4 == 0; }
+static inline dim3 vis_grid(long long n) { return data_grid((n + VIS_PX - 1) / VIS_PX); }
+
 }  // namespace him
 
 using namespace him;
@@ -276,6 +438,54 @@ int him_canvas_paste_window(const void* src, int src_kind, int C, int h, int w, 
   hipLaunchKernelGGL(canvas_paste_window_kernel, data_grid((long long)C * h * w), dim3(256), 0, ST, src, src_kind, C, h,
                      w, canvas, Hc, Wc, x0, y0);
   return check_launch("canvas_paste_window");
+}
+
+int him_tensor2im_bytes(const float* src, int C, int H, int W, int normalize, unsigned char* dst, void* stream) {
+  if (H <= 0 || W <= 0) return fail(HIM_E_INVALID, "tensor2im_bytes: bad shape");
+  if (C != 1 && C != 3) return fail(HIM_E_INVALID, "tensor2im_bytes: %d channels (1 or 3)", C);
+  if (!src || !dst) return fail(HIM_E_INVALID, "tensor2im_bytes: null pointer");
+  const long long n = (long long)H * W;
+  hipLaunchKernelGGL(tensor2im_bytes_kernel, vis_grid(n), dim3(256), 0, ST, src, C, n, normalize ? 1 : 0,
+                     vis_vec(src, n, sizeof(float)) ? 1 : 0, vis_packed(dst) ? 1 : 0, dst);
+  return check_launch("tensor2im_bytes");
+}
+
+int him_label2color_bytes(const void* src, int dtype, int C, int H, int W, const unsigned char* table, int n,
+                          unsigned char* dst, void* stream) {
+  if (C <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "label2color_bytes: bad shape");
+  if (n <= 0 || n > 8192) return fail(HIM_E_INVALID, "label2color_bytes: %d table rows (1..8192)", n);
+  if (!src || !table || !dst) return fail(HIM_E_INVALID, "label2color_bytes: null pointer");
+  if (C > 1 && dtype != 0) return fail(HIM_E_INVALID, "label2color_bytes: scores are fp32 (dtype %d)", dtype);
+  const long long px = (long long)H * W;
+  const dim3 g = vis_grid(px);
+  const size_t lds = (size_t)n * sizeof(unsigned);
+  const int packed = vis_packed(dst) ? 1 : 0;
+  switch (dtype) {
+    case 0: hipLaunchKernelGGL(label2color_bytes_kernel<float>, g, dim3(256), lds, ST, (const float*)src, C, px, table, n,
+                               vis_vec(src, px, sizeof(float)) ? 1 : 0, packed, dst); break;
+    case 1: hipLaunchKernelGGL(label2color_bytes_kernel<unsigned char>, g, dim3(256), lds, ST, (const unsigned char*)src,
+                               C, px, table, n, vis_vec(src, px, 1) ? 1 : 0, packed, dst); break;
+    case 2: hipLaunchKernelGGL(label2color_bytes_kernel<long long>, g, dim3(256), lds, ST, (const long long*)src, C, px,
+                               table, n, vis_vec(src, px, sizeof(long long)) ? 1 : 0, packed, dst); break;
+    default: return fail(HIM_E_INVALID, "label2color_bytes: dtype %d", dtype);
+  }
+  return check_launch("label2color_bytes");
+}
+
+int him_seglabel_bytes(const float* src, int C, int H, int W, unsigned char* dst, void* stream) {
+  if (C <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "seglabel_bytes: bad shape");
+  if (!src || !dst) return fail(HIM_E_INVALID, "seglabel_bytes: null pointer");
+  const long long n = (long long)H * W;
+  const dim3 g = vis_grid(n);
+  const int vec = vis_vec(src, n, sizeof(float)) ? 1 : 0, packed = vis_packed(dst) ? 1 : 0;
+  switch (C) {
+    case 1: hipLaunchKernelGGL(seglabel_bytes_kernel<1>, g, dim3(256), 0, ST, src, C, n, vec, packed, dst); break;
+    case 2: hipLaunchKernelGGL(seglabel_bytes_kernel<2>, g, dim3(256), 0, ST, src, C, n, vec, packed, dst); break;
+    case 3: hipLaunchKernelGGL(seglabel_bytes_kernel<3>, g, dim3(256), 0, ST, src, C, n, vec, packed, dst); break;
+    case 4: hipLaunchKernelGGL(seglabel_bytes_kernel<4>, g, dim3(256), 0, ST, src, C, n, vec, packed, dst); break;
+    default: hipLaunchKernelGGL(seglabel_bytes_kernel<0>, g, dim3(256), 0, ST, src, C, n, vec, packed, dst); break;
+  }
+  return check_launch("seglabel_bytes");
 }
 
 }  // extern "C"

@@ -449,8 +449,17 @@ class Pix2PixHDModel_condImg(BaseModel):
         lib.him_edges(t.data_ptr(), out.data_ptr(), B, H, W, 1, 0, torch.cuda.current_stream().cuda_stream)
         return out
 
-    def get_current_visuals(self):
+    def get_current_visuals(self, as_images=False):
+        """The four tensors of the last step / inference as float CPU tensors, or with ``as_images`` what the reference
+        returns (:293-299): four (H, W, 3) uint8 pictures, converted on the device -- the label from the id map when the
+        condition is a ``LabelCond`` (no one-hot tensor is built), and only the bytes are copied to the host."""
         fake, real, label, cond = self._visuals
+        if as_images:
+            from ..util import util
+            return OrderedDict([('input_label', util.tensor2label(label if isinstance(label, ops.LabelCond) else label[0],
+                                                                  self.opt.label_nc)),
+                                ('input_image', util.tensor2im(cond[0])), ('real_image', util.tensor2im(real[0])),
+                                ('synthesized_image', util.tensor2im(fake[0]))])
         if isinstance(label, ops.LabelCond):
             label = label.full()
         return OrderedDict([('input_label', label[0].cpu()), ('input_image', cond[0].cpu()),

@@ -2237,3 +2237,93 @@ def canvas_paste_window(src, canvas, x0, y0):
     lib.him_canvas_paste_window(_p(src), 1 if src.dtype == torch.int64 else 0, C, src.shape[2], src.shape[3],
                                 _p(canvas), Hc, Wc, int(x0), int(y0), _stream())
     return canvas
+
+
+# -- tensors to pictures: util.util.tensor2im / tensor2label / tensor2seglabel on the device (include/him.h) ------------
+_COLOR_TABLES = {}      # (device index, n_label) -> (device (n,3) uint8 table, the pinned host copy it was uploaded from)
+_ID_DTYPES = {torch.float32: 0, torch.uint8: 1, torch.int64: 2}
+
+
+def _color_table(device, n_label):
+    """``Colorize(n_label)``'s table on ``device``: uploaded once per (device, n) from pinned memory on the current stream
+    (no host synchronisation) and ordered before every later reader on another stream by an event."""
+    from .util.util import labelcolormap
+    n = int(n_label)
+    if n <= 0:
+        raise ValueError('label2color_bytes: n_label must be positive, got %r' % (n_label,))
+    key = (device.index if device.index is not None else torch.cuda.current_device(), n)
+    hit = _COLOR_TABLES.get(key)
+    if hit is None:
+        rows = labelcolormap(n)[:n]
+        host = torch.empty((rows.shape[0], 3), dtype=torch.uint8, pin_memory=True)
+        host.numpy()[...] = rows
+        dev = host.to(device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        hit = _COLOR_TABLES[key] = (dev, host, ev, _stream())
+    elif hit[3] != _stream():
+        torch.cuda.current_stream(device).wait_event(hit[2])
+    return hit[0]
+
+
+def _picture_input(t, what, dtypes, channels=None):
+    if not torch.is_tensor(t) or t.dim() != 3:
+        raise ValueError('%s: a (C, H, W) tensor, got %s' % (what, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+    if channels is not None and t.shape[0] not in channels:
+        raise ValueError('%s: %s channels, got %d' % (what, ' or '.join(str(c) for c in channels), t.shape[0]))
+    if t.dtype not in dtypes:
+        raise ValueError('%s: %s tensor, got %s' % (what, ' / '.join(str(d) for d in dtypes), t.dtype))
+    if 0 in t.shape:
+        raise ValueError('%s: empty tensor %s' % (what, tuple(t.shape)))
+    if not t.is_cuda:
+        t = t.cuda()       # upstream's callers hand in .cpu() tensors
+    return t.detach().contiguous()
+
+
+def tensor2im_bytes(t, normalize=True):
+    """(H, W, 3) uint8 device tensor of a (C, H, W) fp32 image, C = 1 or 3: upstream ``tensor2im``'s bytes (one channel is
+    written three times).  Current stream, no host synchronisation."""
+    t = _picture_input(t, 'tensor2im_bytes', (torch.float32,), channels=(1, 3))
+    C, H, W = t.shape
+    with torch.cuda.device(t.device):
+        dst = torch.empty((H, W, 3), dtype=torch.uint8, device=t.device)
+        lib.him_tensor2im_bytes(_p(t), C, H, W, 1 if normalize else 0, _p(dst), _stream())
+    return dst
+
+
+def label2color_bytes(t, n_label, sample=0):
+    """(H, W, 3) uint8 device tensor: upstream ``tensor2label``'s label branch.  ``t`` (C, H, W): C > 1 fp32 scores (the
+    label is the channel of the maximum, the lowest on a tie), C = 1 an id map (fp32 / uint8 / int64); or a ``LabelCond``,
+    whose id map of batch entry ``sample`` is coloured directly -- the one-hot block is not materialised (its dense
+    channels are edge maps / masked images in [-1, 1]: they never beat the 1.0 of the id's own channel under the
+    lowest-channel tie rule).  Labels outside [0, n_label) are black."""
+    if isinstance(t, LabelCond):
+        t = t.label[sample]
+    if torch.is_tensor(t) and t.dim() == 3 and t.shape[0] > 1 and t.dtype != torch.float32:
+        raise ValueError('label2color_bytes: scores are fp32, got %s' % t.dtype)
+    t = _picture_input(t, 'label2color_bytes', tuple(_ID_DTYPES))
+    C, H, W = t.shape
+    with torch.cuda.device(t.device):
+        table = _color_table(t.device, n_label)
+        dst = torch.empty((H, W, 3), dtype=torch.uint8, device=t.device)
+        lib.him_label2color_bytes(_p(t), _ID_DTYPES[t.dtype], C, H, W, _p(table), table.shape[0], _p(dst), _stream())
+    return dst
+
+
+def seglabel_bytes(t):
+    """(H, W, C) uint8 device tensor of a (C, H, W) fp32 tensor with values in [0, 255]: upstream ``tensor2seglabel``."""
+    t = _picture_input(t, 'seglabel_bytes', (torch.float32,))
+    C, H, W = t.shape
+    with torch.cuda.device(t.device):
+        dst = torch.empty((H, W, C), dtype=torch.uint8, device=t.device)
+        lib.him_seglabel_bytes(_p(t), C, H, W, _p(dst), _stream())
+    return dst
+
+
+def bytes_to_host(dev):
+    """The host ``numpy`` copy of a uint8 device tensor: one asynchronous copy into a pinned buffer and a wait on the
+    current stream only (other streams keep running; nothing but bytes crosses)."""
+    host = torch.empty(dev.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(dev, non_blocking=True)
+    torch.cuda.current_stream(dev.device).synchronize()
+    return host.numpy().copy()

@@ -1,2 +1,2 @@
-"""The reference's ``util`` helpers that the joint box -> layout -> image edit needs (util/data_util.py, util/util.py
-upstream); the visualiser and the HTML writer are not built."""
+"""The reference's ``util`` package: the canvas helpers of the joint box -> layout -> image edit (``data_util``), the script
+reader and the tensor -> picture converters (``util``), the result page (``html``) and the ``Visualizer``."""
