@@ -948,7 +948,8 @@ static int run_fprop(const HimConv2d* d, const float* x, const float* w, const f
   }
   if (wino_fused_fwd_ok(d)) {
     if (!panel) {
-      const size_t need = wino_fused_panel_floats(d->Cout, d->Cin) * sizeof(float);
+      // the size him_conv2d_fwd_ws answers, as on every other path (a workspace one byte short of it is refused)
+      const size_t need = build_only ? wino_fused_panel_floats(d->Cout, d->Cin) * sizeof(float) : fprop_ws_bytes(d);
       if (!ws || ws_bytes < need) return fail(HIM_E_WORKSPACE, "conv fwd needs %zu ws bytes, got %zu", need, ws_bytes);
       hipLaunchKernelGGL((wino_fused_weight_kernel<0>), dim3(cdiv(d->Cin, 256), d->Cout), dim3(256), 0, st, w, (float*)ws,
                          d->Cout, d->Cin);

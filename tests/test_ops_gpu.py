@@ -122,6 +122,20 @@ def test_conv2d_wgrad_splitk_large_spatial():
     assert_close('wgrad split-K', gw, gw_ref, rtol=1e-4)
     (gw2,) = torch.autograd.grad(ops.conv2d(x.to(DEV), wd, None, 1, 1, 'zero', 'none'), (wd,), gy.to(DEV))
     assert torch.equal(gw, gw2), 'wgrad must be run-to-run deterministic'
+    # accumulate mode (the trainer's: dw += into the gradient arena, ops.py _Conv2d.backward) through the C ABI
+    d = ops._conv_desc(x, w, 1, 1, ops.PAD_ZERO, ops.ACT_NONE, 0.0)
+    nb = ops.lib.him_conv2d_bwd_weight_ws(ctypes.byref(d))
+    ws = torch.empty(max(nb, 4) // 4 + 1, dtype=torch.float32, device=DEV)
+    base = _rand(*w.shape, seed=7)
+    xd, gyd, acc = x.to(DEV), gy.to(DEV), []
+    for _ in range(2):
+        dw = base.to(DEV)
+        ops.lib.him_conv2d_bwd_weight(ctypes.byref(d), xd.data_ptr(), gyd.data_ptr(), dw.data_ptr(), 0, 1, ws.data_ptr(), nb,
+                                      torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        acc.append(dw)
+    assert_close('wgrad split-K, accumulate', acc[0], base + gw_ref, rtol=1e-4)
+    assert torch.equal(acc[0], acc[1]), 'accumulating wgrad must be run-to-run deterministic'
 
 
 DECONV_CASES = [(2, 64, 8, 16, 32), (2, 128, 5, 9, 64), (1, 16, 16, 32, 8), (2, 136, 4, 6, 72)]
