@@ -580,6 +580,29 @@ int him_label2color_bytes(const void* src, int dtype, int C, int H, int W, const
                           unsigned char* dst, void* stream);
 int him_seglabel_bytes(const float* src, int C, int H, int W, unsigned char* dst, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Instance-box summary (reference preprocess_city.py:16-41 construct_box): for every instance id >= min_id of an (H,W)
+ * instance plane its inclusive bounding box, its pixel count and int(np.median(classes under it)), in ONE call on the
+ * device.  Integer atomics only (min / max / add commute): results are bit-identical from run to run.
+ *   inst:   (H,W) ids, inst_kind 0 uint8 / 1 16-bit read as unsigned / 2 int32 / 3 int64; accepted ids 0..65535.
+ *   cls:    (H,W) classes, cls_kind 0 uint8 / 1 int32 / 2 int64 / 3 fp32 holding integral values; accepted 0..255.
+ *   status: 2 ints, written by the device: [0] = number of objects found (also when it exceeds max_objects),
+ *           [1] = HIM_INST_OVERFLOW | HIM_INST_ID_RANGE | HIM_INST_CLS_RANGE bits.
+ *   table:  max_objects rows of 7 ints (id, xmin, ymin, xmax, ymax, count, cls), ascending id (np.unique's order),
+ *           rows [0, min(status[0], max_objects)) are written; zero-based inclusive pixel indices; for an even count
+ *           cls is the mean of the two middle order statistics truncated toward zero.  With any status bit set the
+ *           table's contents are unspecified; nothing outside status, table and ws is ever written.
+ *   ws:     him_inst_summary_workspace(H, W, max_objects) bytes, 16-byte aligned; cleared by the call itself, so
+ *           one workspace serves any sequence of calls on one stream.  1 <= max_objects <= 65536.
+ * Planes whose width is not a multiple of 8 or whose base is not 16-byte aligned are read element by element.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_INST_OVERFLOW 1
+#define HIM_INST_ID_RANGE 2
+#define HIM_INST_CLS_RANGE 4
+size_t him_inst_summary_workspace(int H, int W, int max_objects);
+int him_inst_summary(const void* inst, int inst_kind, const void* cls, int cls_kind, int H, int W, int min_id,
+                     int max_objects, int* status, int* table, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -354,6 +354,341 @@ static inline bool vis_vec(const void* src, long long n, size_t elem) {
 static inline bool vis_packed(const void* dst) { return (uintptr_t)dst % 4 == 0; }
 static inline dim3 vis_grid(long long n) { return data_grid((n + VIS_PX - 1) / VIS_PX); }
 
+// ---- instance-box summary (preprocess_city.py construct_box upstream) ---------------------------------------------
+// Workspace (ints): box[5][65536] = xmin | ymin | xmax | ymax | count per id, rowmap[65536] = id -> table row or -1,
+// hist[max_objects][256] = class counts per table row.  Five launches: clear, box pass, compaction (one workgroup),
+// class pass, median.  A lane owns INST_PX adjacent pixels of the flattened plane and folds equal neighbours into runs;
+// a workgroup collects its runs in an LDS hash table and touches the global tables once per distinct key (Guideline 12:
+// partial reduction first); a key the LDS table has no room for goes to the global table directly.  Integer min / max /
+// add only, so arrival order never shows in the result.
+#define INST_IDS 65536
+#define INST_PX 8
+#define INST_BOX_SLOTS 512
+#define INST_CLS_SLOTS 1024
+#define INST_PROBES 8
+
+__device__ __forceinline__ int inst_id(unsigned char v) { return (int)v; }
+__device__ __forceinline__ int inst_id(unsigned short v) { return (int)v; }
+__device__ __forceinline__ int inst_id(int v) { return (v >= 0 && v < INST_IDS) ? v : -2; }
+__device__ __forceinline__ int inst_id(long long v) { return (v >= 0 && v < INST_IDS) ? (int)v : -2; }
+__device__ __forceinline__ int inst_cls(unsigned char v) { return (int)v; }
+__device__ __forceinline__ int inst_cls(int v) { return (v >= 0 && v < 256) ? v : -2; }
+__device__ __forceinline__ int inst_cls(long long v) { return (v >= 0 && v < 256) ? (int)v : -2; }
+__device__ __forceinline__ int inst_cls(float v) { return (v >= 0.0f && v < 256.0f && v == floorf(v)) ? (int)v : -2; }
+
+// v[k] = id / class of pixel i0 + k (-2: outside the accepted domain, -3: behind the plane's end)
+template <typename T, typename F>
+__device__ __forceinline__ void inst_load(const T* __restrict__ plane, long long i0, long long n, bool vec, F conv,
+                                          int v[INST_PX]) {
+  if (vec) {
+    struct alignas(sizeof(T) * INST_PX < 16 ? sizeof(T) * INST_PX : 16) Q { T a[INST_PX]; };
+    const Q q = *(const Q*)(plane + i0);
+#pragma unroll
+    for (int k = 0; k < INST_PX; ++k) v[k] = conv(q.a[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < INST_PX; ++k) v[k] = i0 + k < n ? conv(plane[i0 + k]) : -3;
+  }
+}
+
+__device__ __forceinline__ int inst_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int inst_wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// slot of `key` (>= 0) in an LDS table of SLOTS keys (-1 = free), linear probing; -1: no room within INST_PROBES
+template <int SLOTS>
+__device__ __forceinline__ int inst_slot(int* keys, int key) {
+  const unsigned h = ((unsigned)key * 2654435761u) >> 12;
+#pragma unroll 1
+  for (int p = 0; p < INST_PROBES; ++p) {
+    const int s = (int)((h + p) & (SLOTS - 1));
+    const int old = atomicCAS(&keys[s], -1, key);
+    if (old == -1 || old == key) return s;
+  }
+  return -1;
+}
+
+__global__ void inst_clear_kernel(int* __restrict__ ws, int nhist, int* __restrict__ status) {
+  const int total = 5 * INST_IDS + nhist;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    if (i < 2 * INST_IDS) ws[i] = 0x7fffffff;                 // xmin, ymin
+    else if (i < 4 * INST_IDS) ws[i] = -1;                    // xmax, ymax
+    else if (i < 5 * INST_IDS) ws[i] = 0;                     // count
+    else ws[6 * INST_IDS + (i - 5 * INST_IDS)] = 0;           // hist (rowmap is written whole by the compaction)
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 2) status[threadIdx.x] = 0;
+}
+
+struct InstBoxLds {
+  int key[INST_BOX_SLOTS], xmin[INST_BOX_SLOTS], ymin[INST_BOX_SLOTS], xmax[INST_BOX_SLOTS], ymax[INST_BOX_SLOTS],
+      cnt[INST_BOX_SLOTS];
+};
+
+__device__ __forceinline__ void inst_box_add(InstBoxLds& L, int* __restrict__ box, int id, int x0, int x1, int y0,
+                                             int y1, int n) {
+  const int s = inst_slot<INST_BOX_SLOTS>(L.key, id);
+  if (s >= 0) {
+    atomicMin(&L.xmin[s], x0);
+    atomicMin(&L.ymin[s], y0);
+    atomicMax(&L.xmax[s], x1);
+    atomicMax(&L.ymax[s], y1);
+    atomicAdd(&L.cnt[s], n);
+  } else {
+    atomicMin(&box[id], x0);
+    atomicMin(&box[INST_IDS + id], y0);
+    atomicMax(&box[2 * INST_IDS + id], x1);
+    atomicMax(&box[3 * INST_IDS + id], y1);
+    atomicAdd(&box[4 * INST_IDS + id], n);
+  }
+}
+
+// workgroup b owns the groups [b * per, (b + 1) * per) of INST_PX pixels
+template <typename T>
+__global__ __launch_bounds__(256) void inst_box_kernel(const T* __restrict__ inst, int H, int W, int vec, int min_id,
+                                                       long long per, int* __restrict__ box, int* __restrict__ status) {
+  __shared__ InstBoxLds L;
+  for (int s = threadIdx.x; s < INST_BOX_SLOTS; s += blockDim.x) {
+    L.key[s] = -1;
+    L.xmin[s] = L.ymin[s] = 0x7fffffff;
+    L.xmax[s] = L.ymax[s] = -1;
+    L.cnt[s] = 0;
+  }
+  __syncthreads();
+  const long long n = (long long)H * W, groups = (n + INST_PX - 1) / INST_PX;
+  const long long g0 = blockIdx.x * per, g1 = g0 + per < groups ? g0 + per : groups;
+  bool bad = false;
+  for (long long gb = g0; gb < g1; gb += blockDim.x) {         // the trip count is uniform over the workgroup
+    const long long g = gb + threadIdx.x;
+    const bool active = g < g1;
+    const long long i0 = g * INST_PX;
+    int k[INST_PX];
+    if (active) {
+      inst_load(inst, i0, n, vec != 0, [](T v) { return inst_id(v); }, k);
+    } else {
+#pragma unroll
+      for (int j = 0; j < INST_PX; ++j) k[j] = -3;
+    }
+    bool same = true;
+#pragma unroll
+    for (int j = 0; j < INST_PX; ++j) {
+      bad |= k[j] == -2;
+      k[j] = k[j] >= min_id ? k[j] : -1;                       // below min_id, out of range, behind the end: no object
+      same &= k[j] == k[0];
+    }
+    int x = active ? (int)(i0 % W) : 0, y = active ? (int)(i0 / W) : 0;
+    same &= x + INST_PX <= W;                                  // one row
+    const int first = __shfl(k[0], 0, 64);
+    if (__all(same && k[0] >= 0 && k[0] == first)) {
+      // the whole wave lies inside one object: one update for its 64 * INST_PX pixels
+      const int x0 = inst_wave_min(x), x1 = inst_wave_max(x + INST_PX - 1), y0 = inst_wave_min(y), y1 = inst_wave_max(y);
+      if ((threadIdx.x & 63) == 0) inst_box_add(L, box, k[0], x0, x1, y0, y1, 64 * INST_PX);
+      continue;
+    }
+    int rk = -1, rx = 0, ry = 0, rn = 0;                       // the open run: key, first x, row, length
+#pragma unroll
+    for (int j = 0; j < INST_PX; ++j) {
+      if (k[j] != rk || x == 0) {                              // a run ends with its key or with its row
+        if (rk >= 0) inst_box_add(L, box, rk, rx, rx + rn - 1, ry, ry, rn);
+        rk = k[j]; rx = x; ry = y; rn = 0;
+      }
+      ++rn;
+      if (++x == W) { x = 0; ++y; }
+    }
+    if (rk >= 0) inst_box_add(L, box, rk, rx, rx + rn - 1, ry, ry, rn);
+  }
+  if (bad) atomicOr(&status[1], HIM_INST_ID_RANGE);
+  __syncthreads();
+  for (int s = threadIdx.x; s < INST_BOX_SLOTS; s += blockDim.x) {
+    const int id = L.key[s];
+    if (id < 0) continue;
+    atomicMin(&box[id], L.xmin[s]);
+    atomicMin(&box[INST_IDS + id], L.ymin[s]);
+    atomicMax(&box[2 * INST_IDS + id], L.xmax[s]);
+    atomicMax(&box[3 * INST_IDS + id], L.ymax[s]);
+    atomicAdd(&box[4 * INST_IDS + id], L.cnt[s]);
+  }
+}
+
+// One workgroup of 1024 threads, 64 ids each: the present ids in ascending order -> table rows and the id -> row map
+__global__ __launch_bounds__(1024) void inst_compact_kernel(const int* __restrict__ box, int* __restrict__ rowmap,
+                                                            int max_objects, int* __restrict__ status,
+                                                            int* __restrict__ table) {
+  __shared__ int wave_total[16];
+  const int t = threadIdx.x, lane = t & 63;
+  const int* cnt = box + 4 * INST_IDS;
+  unsigned long long present = 0ull;
+  int mine = 0;
+  for (int j = 0; j < 64; ++j)
+    if (cnt[t * 64 + j] > 0) { present |= 1ull << j; ++mine; }
+  int inc = mine;                                              // inclusive scan over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (lane == 63) wave_total[t >> 6] = inc;
+  __syncthreads();
+  int row = inc - mine, total = 0;
+  for (int w = 0; w < 16; ++w) {
+    if (w < (t >> 6)) row += wave_total[w];
+    total += wave_total[w];
+  }
+  for (int j = 0; j < 64; ++j) {
+    const int id = t * 64 + j;
+    int r = -1;
+    if ((present >> j) & 1ull) {
+      if (row < max_objects) {
+        r = row;
+        int* o = table + (long long)r * 7;
+        o[0] = id;
+        o[1] = box[id];
+        o[2] = box[INST_IDS + id];
+        o[3] = box[2 * INST_IDS + id];
+        o[4] = box[3 * INST_IDS + id];
+        o[5] = cnt[id];
+        o[6] = 0;
+      }
+      ++row;
+    }
+    rowmap[id] = r;
+  }
+  if (t == 0) {
+    status[0] = total;
+    if (total > max_objects) status[1] |= HIM_INST_OVERFLOW;
+  }
+}
+
+struct InstClsLds {
+  int key[INST_CLS_SLOTS], cnt[INST_CLS_SLOTS];
+};
+
+// key = id << 8 | class
+__device__ __forceinline__ void inst_cls_add(InstClsLds& L, const int* __restrict__ rowmap, int* __restrict__ hist,
+                                             int key, int n) {
+  const int s = inst_slot<INST_CLS_SLOTS>(L.key, key);
+  if (s >= 0) {
+    atomicAdd(&L.cnt[s], n);
+  } else {
+    const int row = rowmap[key >> 8];
+    if (row >= 0) atomicAdd(&hist[row * 256 + (key & 255)], n);
+  }
+}
+
+template <typename T, typename C>
+__global__ __launch_bounds__(256) void inst_class_kernel(const T* __restrict__ inst, const C* __restrict__ cls, int H,
+                                                         int W, int vec, int min_id, long long per,
+                                                         const int* __restrict__ rowmap, int* __restrict__ hist,
+                                                         int* __restrict__ status) {
+  __shared__ InstClsLds L;
+  for (int s = threadIdx.x; s < INST_CLS_SLOTS; s += blockDim.x) {
+    L.key[s] = -1;
+    L.cnt[s] = 0;
+  }
+  __syncthreads();
+  const long long n = (long long)H * W, groups = (n + INST_PX - 1) / INST_PX;
+  const long long g0 = blockIdx.x * per, g1 = g0 + per < groups ? g0 + per : groups;
+  bool bad = false;
+  for (long long gb = g0; gb < g1; gb += blockDim.x) {
+    const long long g = gb + threadIdx.x;
+    const bool active = g < g1;
+    const long long i0 = g * INST_PX;
+    int k[INST_PX], c[INST_PX];
+    if (active) {
+      inst_load(inst, i0, n, vec != 0, [](T v) { return inst_id(v); }, k);
+      inst_load(cls, i0, n, vec != 0, [](C v) { return inst_cls(v); }, c);
+    } else {
+#pragma unroll
+      for (int j = 0; j < INST_PX; ++j) k[j] = c[j] = -3;
+    }
+    bool same = true;
+#pragma unroll
+    for (int j = 0; j < INST_PX; ++j) {
+      bad |= c[j] == -2;
+      k[j] = (k[j] >= min_id && c[j] >= 0) ? ((k[j] << 8) | c[j]) : -1;
+      same &= k[j] == k[0];
+    }
+    const int first = __shfl(k[0], 0, 64);
+    if (__all(same && k[0] >= 0 && k[0] == first)) {
+      if ((threadIdx.x & 63) == 0) inst_cls_add(L, rowmap, hist, k[0], 64 * INST_PX);
+      continue;
+    }
+    int rk = -1, rn = 0;
+#pragma unroll
+    for (int j = 0; j < INST_PX; ++j) {
+      if (k[j] != rk) {
+        if (rk >= 0) inst_cls_add(L, rowmap, hist, rk, rn);
+        rk = k[j]; rn = 0;
+      }
+      ++rn;
+    }
+    if (rk >= 0) inst_cls_add(L, rowmap, hist, rk, rn);
+  }
+  if (bad) atomicOr(&status[1], HIM_INST_CLS_RANGE);
+  __syncthreads();
+  for (int s = threadIdx.x; s < INST_CLS_SLOTS; s += blockDim.x) {
+    const int key = L.key[s];
+    if (key < 0) continue;
+    const int row = rowmap[key >> 8];
+    if (row >= 0) atomicAdd(&hist[row * 256 + (key & 255)], L.cnt[s]);
+  }
+}
+
+// one wave per table row: the two middle order statistics of its 256 bins, cls = (lo + hi) >> 1
+__global__ __launch_bounds__(256) void inst_median_kernel(const int* __restrict__ hist, const int* __restrict__ status,
+                                                          int max_objects, int* __restrict__ table) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int rows = status[0] < max_objects ? status[0] : max_objects;
+  if (row >= rows) return;                                     // whole waves leave; no barrier below
+  const int4 h = ((const int4*)(hist + row * 256))[lane];
+  const int mine = h.x + h.y + h.z + h.w;
+  int inc = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  const int n = table[row * 7 + 5], klo = (n - 1) >> 1, khi = n >> 1;
+  const int bins[4] = {h.x, h.y, h.z, h.w};
+  int lo = -1, hi = -1, before = inc - mine;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int upto = before + bins[q];
+    if (klo >= before && klo < upto) lo = lane * 4 + q;
+    if (khi >= before && khi < upto) hi = lane * 4 + q;
+    before = upto;
+  }
+  lo = inst_wave_max(lo);
+  hi = inst_wave_max(hi);
+  if (lane == 0) table[row * 7 + 6] = (lo < 0 || hi < 0) ? 0 : (lo + hi) >> 1;   // not found: pixels outside the class domain
+}
+
+static inline size_t inst_ws_bytes(int max_objects) {
+  return ((size_t)6 * INST_IDS + (size_t)max_objects * 256) * sizeof(int);
+}
+static inline bool inst_vec(const void* p, int W) { return W % INST_PX == 0 && (uintptr_t)p % 16 == 0; }
+
+template <typename T>
+static void inst_launch_class(const T* inst, const void* cls, int cls_kind, int H, int W, int vec, int min_id,
+                              long long per, dim3 grid, const int* rowmap, int* hist, int* status, hipStream_t st) {
+  switch (cls_kind) {
+    case 0: hipLaunchKernelGGL((inst_class_kernel<T, unsigned char>), grid, dim3(256), 0, st, inst,
+                               (const unsigned char*)cls, H, W, vec, min_id, per, rowmap, hist, status); break;
+    case 1: hipLaunchKernelGGL((inst_class_kernel<T, int>), grid, dim3(256), 0, st, inst, (const int*)cls, H, W, vec,
+                               min_id, per, rowmap, hist, status); break;
+    case 2: hipLaunchKernelGGL((inst_class_kernel<T, long long>), grid, dim3(256), 0, st, inst, (const long long*)cls, H,
+                               W, vec, min_id, per, rowmap, hist, status); break;
+    default: hipLaunchKernelGGL((inst_class_kernel<T, float>), grid, dim3(256), 0, st, inst, (const float*)cls, H, W,
+                                vec, min_id, per, rowmap, hist, status); break;
+  }
+}
+
 }  // namespace him
 
 using namespace him;
@@ -486,6 +821,59 @@ int him_seglabel_bytes(const float* src, int C, int H, int W, unsigned char* dst
     default: hipLaunchKernelGGL(seglabel_bytes_kernel<0>, g, dim3(256), 0, ST, src, C, n, vec, packed, dst); break;
   }
   return check_launch("seglabel_bytes");
+}
+
+size_t him_inst_summary_workspace(int H, int W, int max_objects) {
+  if (H <= 0 || W <= 0 || max_objects <= 0 || max_objects > INST_IDS) return 0;
+  return inst_ws_bytes(max_objects);
+}
+
+int him_inst_summary(const void* inst, int inst_kind, const void* cls, int cls_kind, int H, int W, int min_id,
+                     int max_objects, int* status, int* table, void* ws, size_t ws_bytes, void* stream) {
+  if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return fail(HIM_E_INVALID, "inst_summary: bad shape");
+  if (max_objects <= 0 || max_objects > INST_IDS)
+    return fail(HIM_E_INVALID, "inst_summary: max_objects %d (1..%d)", max_objects, INST_IDS);
+  if (!inst || !cls || !status || !table || !ws) return fail(HIM_E_INVALID, "inst_summary: null pointer");
+  if (inst_kind < 0 || inst_kind > 3) return fail(HIM_E_INVALID, "inst_summary: inst_kind %d", inst_kind);
+  if (cls_kind < 0 || cls_kind > 3) return fail(HIM_E_INVALID, "inst_summary: cls_kind %d", cls_kind);
+  if ((uintptr_t)ws % 16 != 0) return fail(HIM_E_INVALID, "inst_summary: workspace not 16-byte aligned");
+  if (ws_bytes < inst_ws_bytes(max_objects))
+    return fail(HIM_E_INVALID, "inst_summary: workspace %zu < %zu bytes", ws_bytes, inst_ws_bytes(max_objects));
+  if (min_id < 0) min_id = 0;
+  int* box = (int*)ws;
+  int* rowmap = box + 5 * INST_IDS;
+  int* hist = box + 6 * INST_IDS;
+  const long long groups = ((long long)H * W + INST_PX - 1) / INST_PX;
+  long long blocks = (groups + 511) / 512;
+  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  const long long per = (groups + blocks - 1) / blocks;
+  const dim3 grid((unsigned)blocks);
+  const int nhist = max_objects * 256;
+  hipLaunchKernelGGL(inst_clear_kernel, data_grid(5 * INST_IDS + (long long)nhist), dim3(256), 0, ST, box, nhist, status);
+  const int bvec = inst_vec(inst, W) ? 1 : 0, cvec = (bvec && inst_vec(cls, W)) ? 1 : 0;
+  switch (inst_kind) {
+    case 0: hipLaunchKernelGGL(inst_box_kernel<unsigned char>, grid, dim3(256), 0, ST, (const unsigned char*)inst, H, W,
+                               bvec, min_id, per, box, status); break;
+    case 1: hipLaunchKernelGGL(inst_box_kernel<unsigned short>, grid, dim3(256), 0, ST, (const unsigned short*)inst, H, W,
+                               bvec, min_id, per, box, status); break;
+    case 2: hipLaunchKernelGGL(inst_box_kernel<int>, grid, dim3(256), 0, ST, (const int*)inst, H, W, bvec, min_id, per,
+                               box, status); break;
+    default: hipLaunchKernelGGL(inst_box_kernel<long long>, grid, dim3(256), 0, ST, (const long long*)inst, H, W, bvec,
+                                min_id, per, box, status); break;
+  }
+  hipLaunchKernelGGL(inst_compact_kernel, dim3(1), dim3(1024), 0, ST, box, rowmap, max_objects, status, table);
+  switch (inst_kind) {
+    case 0: inst_launch_class((const unsigned char*)inst, cls, cls_kind, H, W, cvec, min_id, per, grid, rowmap, hist,
+                              status, ST); break;
+    case 1: inst_launch_class((const unsigned short*)inst, cls, cls_kind, H, W, cvec, min_id, per, grid, rowmap, hist,
+                              status, ST); break;
+    case 2: inst_launch_class((const int*)inst, cls, cls_kind, H, W, cvec, min_id, per, grid, rowmap, hist, status, ST);
+      break;
+    default: inst_launch_class((const long long*)inst, cls, cls_kind, H, W, cvec, min_id, per, grid, rowmap, hist,
+                               status, ST); break;
+  }
+  hipLaunchKernelGGL(inst_median_kernel, dim3((max_objects + 3) / 4), dim3(256), 0, ST, hist, status, max_objects, table);
+  return check_launch("inst_summary");
 }
 
 }  // extern "C"

@@ -2327,3 +2327,73 @@ def bytes_to_host(dev):
     host.copy_(dev, non_blocking=True)
     torch.cuda.current_stream(dev.device).synchronize()
     return host.numpy().copy()
+
+
+# -- instance-box summary: preprocess_city.construct_box's per-instance loop in one device call (include/him.h) ---------
+_INST_KINDS = {torch.uint8: 0, torch.int16: 1, torch.uint16: 1, torch.int32: 2, torch.int64: 3}
+_CLS_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
+_INST_FLAGS = ((1, 'more than max_objects=%(max)d objects (%(count)d found)'),
+               (2, 'an instance id outside 0..65535'),
+               (4, 'a class value outside 0..255 (or not integral)'))
+_INST_STATE = {}        # (H, W, max_objects, device index) -> workspace, status + table, pinned host copy, event, stream
+
+
+def _inst_plane(t, what, kinds):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('inst_summary: %s must be a device tensor' % what)
+    if t.dtype not in kinds:
+        raise ValueError('inst_summary: %s is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in kinds)))
+    if t.dim() < 2 or any(s != 1 for s in t.shape[:-2]) or 0 in t.shape:
+        raise ValueError('inst_summary: %s must be one (H, W) plane, got %s' % (what, tuple(t.shape)))
+    return t.detach().reshape(t.shape[-2], t.shape[-1]).contiguous()
+
+
+def inst_summary_launch(inst, cls, min_id=1000, max_objects=1024):
+    """Queue the device pass on the current stream; returns the cached state whose ``out`` tensor (2 status ints, then
+    ``max_objects`` rows of 7) the kernels fill.  No copy, no host synchronisation (``inst_summary`` adds both)."""
+    inst = _inst_plane(inst, 'inst', _INST_KINDS)
+    cls = _inst_plane(cls, 'cls', _CLS_KINDS)
+    if inst.shape != cls.shape or inst.device != cls.device:
+        raise ValueError('inst_summary: inst %s on %s and cls %s on %s differ' % (tuple(inst.shape), inst.device,
+                                                                                tuple(cls.shape), cls.device))
+    H, W = inst.shape
+    max_objects = int(max_objects)
+    if not 1 <= max_objects <= 65536:
+        raise ValueError('inst_summary: max_objects must be in 1..65536, got %d' % max_objects)
+    with torch.cuda.device(inst.device):
+        key = (H, W, max_objects, torch.cuda.current_device())
+        st = _INST_STATE.get(key)
+        if st is None:
+            nws = int(lib.him_inst_summary_workspace(H, W, max_objects))
+            st = _INST_STATE[key] = dict(
+                ws=torch.empty(nws, dtype=torch.uint8, device=inst.device), nws=nws,
+                out=torch.empty(2 + 7 * max_objects, dtype=torch.int32, device=inst.device),
+                host=torch.empty(2 + 7 * max_objects, dtype=torch.int32, pin_memory=True),
+                event=torch.cuda.Event(), stream=None)
+        elif st['stream'] != _stream():
+            torch.cuda.current_stream().wait_event(st['event'])      # the previous user of this workspace, elsewhere
+        out = st['out']
+        lib.him_inst_summary(_p(inst), _INST_KINDS[inst.dtype], _p(cls), _CLS_KINDS[cls.dtype], H, W, int(min_id),
+                             max_objects, _p(out), _p(out) + 8, _p(st['ws']), st['nws'], _stream())
+        st['stream'] = _stream()
+        st['event'].record(torch.cuda.current_stream())
+    return st
+
+
+def inst_summary(inst, cls, min_id=1000, max_objects=1024):
+    """(n, 7) host ``int32`` rows ``id, xmin, ymin, xmax, ymax, count, cls`` of every instance id >= ``min_id`` of the
+    device plane ``inst`` (uint8 / 16-bit read as unsigned / int32 / int64, ids 0..65535), ascending id; the box is
+    inclusive, ``cls = int(np.median(cls[inst == id]))`` of the device plane ``cls`` (uint8 / int32 / int64 / integral
+    fp32, 0..255) -- what upstream's ``construct_box`` stores per object.  One asynchronous copy of status + table into a
+    pinned buffer and one wait on the current stream.  ``ValueError`` names an overflow or a value outside its domain."""
+    st = inst_summary_launch(inst, cls, min_id, max_objects)
+    with torch.cuda.device(st['out'].device):
+        st['host'].copy_(st['out'], non_blocking=True)
+        st['event'].record(torch.cuda.current_stream())
+        torch.cuda.current_stream().synchronize()
+    host = st['host'].numpy()
+    count, flags = int(host[0]), int(host[1])
+    if flags:
+        why = [text % dict(max=int(max_objects), count=count) for bit, text in _INST_FLAGS if flags & bit]
+        raise ValueError('inst_summary: ' + '; '.join(why))
+    return host[2:2 + 7 * count].reshape(count, 7).copy()

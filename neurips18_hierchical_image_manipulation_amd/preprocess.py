@@ -1,0 +1,130 @@
+"""Cityscapes preprocessing: sort a raw download into the ``<phase>_img / _label / _inst`` folders the loader reads and
+write the ``<phase>_bbox/<stem>.json`` box tables (upstream's ``preprocess_city.py``), with the per-instance work on the
+device: one ``ops.inst_summary`` call per image pair instead of two full-map compares, a ``where`` and a median per
+instance.
+
+    python -m neurips18_hierchical_image_manipulation_amd.preprocess --dataroot datasets/cityscape
+
+``construct_box`` writes the bytes upstream writes (same keys, same order, default ``json.dump`` layout); ``inst_info``
+builds the same dict from maps that already live on the device, e.g. the canvases of a ``JointInference`` edit.
+"""
+import argparse
+import glob
+import json
+import os
+from concurrent.futures import ThreadPoolExecutor
+from shutil import copy2
+
+import numpy as np
+from PIL import Image
+
+DECODE_THREADS = 4      # PNG decoding leaves the interpreter lock; a fixed, small pool (never sized by the host's CPU count)
+PREFETCH = 4            # pairs decoded ahead of the device pass
+MIN_ID = 1000           # upstream's threshold: Cityscapes stores classes without instances under ids below it
+MAX_OBJECTS = 1024      # per image; more raises (ops.inst_summary names the overflow)
+
+
+def copy_file(src, src_ext, dst):
+    """Copy every ``<src>/*/<src_ext>`` file into ``dst`` (sorted order)."""
+    for path in sorted(glob.glob(os.path.join(src, '*', src_ext))):
+        copy2(path, dst)
+        print('copied %s to %s' % (path, dst))
+
+
+def _decode(path):
+    """A single-channel map file as the narrowest unsigned array that holds it (uint8 or uint16; int32 otherwise)."""
+    with Image.open(path) as im:
+        a = np.array(im)
+    if a.ndim != 2:
+        raise ValueError('%s: a single-channel map is expected, got mode %s' % (path, im.mode))
+    if a.dtype == np.bool_:
+        return a.astype(np.uint8)
+    if a.dtype in (np.uint8, np.uint16):
+        return np.ascontiguousarray(a)
+    if a.dtype.kind not in 'iu':
+        raise ValueError('%s: an integer map is expected, got %s' % (path, a.dtype))
+    if a.size and 0 <= int(a.min()) and int(a.max()) <= 65535:
+        return a.astype(np.uint16)
+    return a.astype(np.int32)
+
+
+def _decode_pair(inst_path, cls_path):
+    return _decode(inst_path), _decode(cls_path)
+
+
+def rows_to_info(H, W, rows):
+    """The dict upstream dumps: plain Python ints, objects in the rows' (ascending id) order."""
+    objects = {}
+    for r in rows:
+        objects[str(int(r[0]))] = {'bbox': [int(r[1]), int(r[2]), int(r[3]), int(r[4])], 'cls': int(r[6])}
+    return {'imgHeight': int(H), 'imgWidth': int(W), 'objects': objects}
+
+
+def write_info(path, info):
+    with open(path, 'w') as f:
+        json.dump(info, f)
+
+
+def _device_plane(a, device):
+    import torch
+    return torch.from_numpy(a).to(device)        # in the file's own width: uint8 / uint16 cross, not int32
+
+
+def inst_info(inst, label, min_id=MIN_ID):
+    """The box table of instance / label maps that are already on the device (any shape with one (H, W) plane; fp32 maps
+    holding integers, as the loader and the joint edit keep them, are accepted).  Writes no file."""
+    import torch
+    from . import ops
+    if inst.dtype == torch.float32:
+        inst = inst.to(torch.int32)
+    rows = ops.inst_summary(inst, label, min_id=min_id, max_objects=MAX_OBJECTS)
+    return rows_to_info(inst.shape[-2], inst.shape[-1], rows)
+
+
+def construct_box(inst_root, inst_name, cls_name, dst, device=None):
+    """For every (instance map, class map) pair ``<inst_root>/*/<inst_name>``, ``<inst_root>/*/<cls_name>`` (each list
+    sorted, then zipped) write ``<dst>/<instance file stem>.json``.  Files are decoded on a small thread pool a few pairs
+    ahead, so decoding overlaps the device pass and the JSON writing of the pair in hand."""
+    import torch
+    from . import ops
+    inst_list = sorted(glob.glob(os.path.join(inst_root, '*', inst_name)))
+    cls_list = sorted(glob.glob(os.path.join(inst_root, '*', cls_name)))
+    pairs = list(zip(inst_list, cls_list))
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
+        pending = [pool.submit(_decode_pair, *p) for p in pairs[:PREFETCH]]
+        for i, (inst_path, _) in enumerate(pairs):
+            inst_map, cls_map = pending.pop(0).result()
+            if i + PREFETCH < len(pairs):
+                pending.append(pool.submit(_decode_pair, *pairs[i + PREFETCH]))
+            if inst_map.shape != cls_map.shape:
+                raise ValueError('%s: instance map %s and class map %s differ in size' % (inst_path, inst_map.shape,
+                                                                                        cls_map.shape))
+            rows = ops.inst_summary(_device_plane(inst_map, device), _device_plane(cls_map, device), min_id=MIN_ID,
+                                    max_objects=MAX_OBJECTS)
+            H, W = inst_map.shape
+            savename = os.path.join(dst, os.path.splitext(os.path.basename(inst_path))[0] + '.json')
+            write_info(savename, rows_to_info(H, W, rows))
+            print('wrote a bbox summary of %s to %s' % (inst_path, savename))
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='Organise a raw Cityscapes download and write the box tables.')
+    parser.add_argument('--dataroot', default='datasets/cityscape',
+                        help='holds leftImg8bit/ and gtFine/; the <phase>_* folders are created inside it')
+    opt = parser.parse_args(argv)
+    root = opt.dataroot
+    for phase in ('train', 'val'):
+        for sub in ('img', 'label', 'inst', 'bbox'):
+            os.makedirs(os.path.join(root, '%s_%s' % (phase, sub)), exist_ok=True)
+    for phase in ('train', 'val'):
+        copy_file(os.path.join(root, 'leftImg8bit', phase), '*_leftImg8bit.png', os.path.join(root, phase + '_img'))
+        copy_file(os.path.join(root, 'gtFine', phase), '*_labelIds.png', os.path.join(root, phase + '_label'))
+        copy_file(os.path.join(root, 'gtFine', phase), '*_instanceIds.png', os.path.join(root, phase + '_inst'))
+    for phase in ('train', 'val'):
+        construct_box(os.path.join(root, 'gtFine', phase), '*_instanceIds.png', '*_labelIds.png',
+                      os.path.join(root, phase + '_bbox'))
+
+
+if __name__ == '__main__':
+    main()
