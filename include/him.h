@@ -603,6 +603,31 @@ size_t him_inst_summary_workspace(int H, int W, int max_objects);
 int him_inst_summary(const void* inst, int inst_kind, const void* cls, int cls_kind, int H, int W, int min_id,
                      int max_objects, int* status, int* table, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ADE20K segmentation decode (reference preprocess_ade.py: loadAde20K, and the relabel and box loops of its main): the
+ * colour planes of one `_seg.png` to a class plane, a label plane, an instance-rank plane and a box per instance, in ONE
+ * call on the device.  Integer atomics only (min / max / add): results are bit-identical from run to run.
+ *   seg:       (H,W,pixel_bytes) interleaved bytes R,G,B[,A] as the PNG decodes; pixel_bytes 3 or 4, a fourth byte is
+ *              ignored.  Never written.
+ *   keep:      n_keep (0..255) class ids on the device; may be NULL when n_keep is 0.
+ *   cls_out:   (H,W) uint16 raw class (R / 10) * 256 + G, the division flooring; may be NULL.
+ *   label_out: (H,W) bytes: the 1-based position of the class in keep (of its first occurrence), 0 when it is not there.
+ *   inst_out:  (H,W) bytes: the rank of the pixel's B value among the distinct B values of the image
+ *              (np.unique(B, return_inverse=True)); rank 0 is the lowest value present, zero or not.
+ *   status:    2 ints: [0] = number of distinct B values (1..256), [1] = flags, 0 (reserved).
+ *   table:     256 rows of 7 ints (rank, b, xmin, ymin, xmax, ymax, count), ascending rank, zero-based inclusive pixel
+ *              indices; rows [0, status[0]) are written and nothing behind them.
+ *   ws:        him_ade_decode_workspace() bytes, 16-byte aligned; cleared by the call itself, so one workspace serves
+ *              any sequence of calls on one stream.
+ * Three launches on `stream`, no host synchronisation.  Nothing outside the five outputs and ws is written.  With every
+ * plane's base on a 16-byte boundary whole 16-pixel groups move as 16-byte words; any other base, and the last partial
+ * group of a plane, is read and written byte by byte.  H * W <= 2^31 - 1.
+ * ------------------------------------------------------------------------------------------- */
+size_t him_ade_decode_workspace(void);
+int him_ade_decode(const unsigned char* seg, int H, int W, int pixel_bytes, const unsigned short* keep, int n_keep,
+                   unsigned short* cls_out, unsigned char* label_out, unsigned char* inst_out, int* status, int* table,
+                   void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

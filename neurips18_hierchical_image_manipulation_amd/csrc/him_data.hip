@@ -689,6 +689,198 @@ static void inst_launch_class(const T* inst, const void* cls, int cls_kind, int 
   }
 }
 
+// ---- ADE20K segmentation decode (reference preprocess_ade.py loadAde20K + the relabel / box loops of its main) ----------
+// Three launches: setup (clear the 256 bins, build the class -> label table), first pass (classes, labels, the raw B
+// plane and a box + count per B value), second pass (B values present -> ranks: table, status, the B plane mapped in
+// place).  A lane owns ADE_PX adjacent pixels of the flattened image; on the vector path it reads them as whole 16-byte
+// words (ADE_PX * pixel_bytes = 48 or 64 bytes) and stores each output as 16-byte words, on the element path byte by
+// byte with a bound per pixel -- the same code behind both.  B runs are folded before they reach the 256 LDS bins, and a
+// workgroup flushes only the bins it touched.  Integer min / max / add only.
+#define ADE_PX 16
+#define ADE_BINS 256
+#define ADE_CLASSES 6656                                       // (255 / 10) * 256 + 255 + 1 raw class values
+#define ADE_WS_BYTES ((size_t)5 * ADE_BINS * sizeof(int) + ADE_CLASSES)
+
+struct AdeLds {
+  alignas(16) unsigned char lut[ADE_CLASSES];
+  int xmin[ADE_BINS], ymin[ADE_BINS], xmax[ADE_BINS], ymax[ADE_BINS], cnt[ADE_BINS];
+};
+
+// one workgroup: bins to their neutral values; lut[class] = 1-based position of its FIRST occurrence in keep, else 0
+__global__ __launch_bounds__(256) void ade_setup_kernel(const unsigned short* __restrict__ keep, int n_keep,
+                                                        int* __restrict__ bins, unsigned char* __restrict__ lut) {
+  __shared__ alignas(16) unsigned char table[ADE_CLASSES];
+  __shared__ unsigned short k[256];
+  const int t = threadIdx.x;
+  bins[t] = bins[ADE_BINS + t] = 0x7fffffff;
+  bins[2 * ADE_BINS + t] = bins[3 * ADE_BINS + t] = -1;
+  bins[4 * ADE_BINS + t] = 0;
+  for (int i = t; i < ADE_CLASSES / 4; i += 256) ((unsigned*)table)[i] = 0u;
+  k[t] = t < n_keep ? keep[t] : (unsigned short)0;
+  __syncthreads();
+  if (t < n_keep && k[t] < ADE_CLASSES) {
+    bool first = true;
+    for (int i = 0; i < t; ++i) first &= k[i] != k[t];
+    if (first) table[k[t]] = (unsigned char)(t + 1);
+  }
+  __syncthreads();
+  for (int i = t; i < ADE_CLASSES / 4; i += 256) ((unsigned*)lut)[i] = ((const unsigned*)table)[i];
+}
+
+__device__ __forceinline__ void ade_box_add(AdeLds& L, int b, int x0, int x1, int y0, int y1, int n) {
+  atomicMin(&L.xmin[b], x0);
+  atomicMin(&L.ymin[b], y0);
+  atomicMax(&L.xmax[b], x1);
+  atomicMax(&L.ymax[b], y1);
+  atomicAdd(&L.cnt[b], n);
+}
+
+// workgroup b owns the groups [b * per, (b + 1) * per) of ADE_PX pixels; PB = bytes per pixel (3 or 4)
+template <int PB>
+__global__ __launch_bounds__(256) void ade_first_kernel(const unsigned char* __restrict__ seg, int H, int W, int vec,
+                                                        long long per, const unsigned char* __restrict__ lut,
+                                                        unsigned short* __restrict__ cls_out,
+                                                        unsigned char* __restrict__ label_out,
+                                                        unsigned char* __restrict__ inst_out, int* __restrict__ bins) {
+  __shared__ AdeLds L;
+  for (int i = threadIdx.x; i < ADE_CLASSES / 16; i += blockDim.x) ((uint4*)L.lut)[i] = ((const uint4*)lut)[i];
+  for (int s = threadIdx.x; s < ADE_BINS; s += blockDim.x) {
+    L.xmin[s] = L.ymin[s] = 0x7fffffff;
+    L.xmax[s] = L.ymax[s] = -1;
+    L.cnt[s] = 0;
+  }
+  __syncthreads();
+  const long long n = (long long)H * W, groups = (n + ADE_PX - 1) / ADE_PX;
+  const long long g0 = blockIdx.x * per, g1 = g0 + per < groups ? g0 + per : groups;
+  struct alignas(16) In { unsigned char a[ADE_PX * PB]; };
+  struct alignas(16) Out8 { unsigned char a[ADE_PX]; };
+  struct alignas(16) Out16 { unsigned short a[ADE_PX]; };
+  for (long long gb = g0; gb < g1; gb += blockDim.x) {         // the trip count is uniform over the workgroup
+    const long long g = gb + threadIdx.x;
+    const bool active = g < g1;
+    const long long i0 = g * ADE_PX;
+    const int m = !active ? 0 : (n - i0 < ADE_PX ? (int)(n - i0) : ADE_PX);      // pixels of this group inside the plane
+    const bool whole = vec != 0 && m == ADE_PX;
+    In in;
+    if (whole) {
+      in = *(const In*)(seg + i0 * PB);
+    } else {
+#pragma unroll
+      for (int k = 0; k < ADE_PX; ++k) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) in.a[k * PB + c] = k < m ? seg[(i0 + k) * PB + c] : (unsigned char)0;
+      }
+    }
+    Out16 oc;
+    Out8 ol, ob;
+#pragma unroll
+    for (int k = 0; k < ADE_PX; ++k) {
+      const int c = (in.a[k * PB] / 10) * 256 + in.a[k * PB + 1];
+      oc.a[k] = (unsigned short)c;
+      ol.a[k] = L.lut[c];
+      ob.a[k] = in.a[k * PB + 2];
+    }
+    if (whole) {
+      if (cls_out) *(Out16*)(cls_out + i0) = oc;
+      *(Out8*)(label_out + i0) = ol;
+      *(Out8*)(inst_out + i0) = ob;
+    } else {
+#pragma unroll
+      for (int k = 0; k < ADE_PX; ++k) {
+        if (k < m) {
+          if (cls_out) cls_out[i0 + k] = oc.a[k];
+          label_out[i0 + k] = ol.a[k];
+          inst_out[i0 + k] = ob.a[k];
+        }
+      }
+    }
+    int x = active ? (int)(i0 % W) : 0, y = active ? (int)(i0 / W) : 0;
+    bool same = m == ADE_PX && x + ADE_PX <= W;                // a whole group inside one row
+#pragma unroll
+    for (int k = 1; k < ADE_PX; ++k) same &= ob.a[k] == ob.a[0];
+    const int first = __shfl((int)ob.a[0], 0, 64);
+    if (__all(same && (int)ob.a[0] == first)) {
+      // the whole wave lies inside one instance: one update for its 64 * ADE_PX pixels
+      const int x0 = inst_wave_min(x), x1 = inst_wave_max(x + ADE_PX - 1), y0 = inst_wave_min(y), y1 = inst_wave_max(y);
+      if ((threadIdx.x & 63) == 0) ade_box_add(L, first, x0, x1, y0, y1, 64 * ADE_PX);
+      continue;
+    }
+    int rk = -1, rx = 0, ry = 0, rn = 0;                       // the open run: B value, first x, row, length
+#pragma unroll
+    for (int k = 0; k < ADE_PX; ++k) {
+      if (k < m) {
+        if ((int)ob.a[k] != rk || x == 0) {                    // a run ends with its value or with its row
+          if (rk >= 0) ade_box_add(L, rk, rx, rx + rn - 1, ry, ry, rn);
+          rk = ob.a[k]; rx = x; ry = y; rn = 0;
+        }
+        ++rn;
+        if (++x == W) { x = 0; ++y; }
+      }
+    }
+    if (rk >= 0) ade_box_add(L, rk, rx, rx + rn - 1, ry, ry, rn);
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < ADE_BINS; s += blockDim.x) {
+    if (L.cnt[s] == 0) continue;                               // only the bins this workgroup touched
+    atomicMin(&bins[s], L.xmin[s]);
+    atomicMin(&bins[ADE_BINS + s], L.ymin[s]);
+    atomicMax(&bins[2 * ADE_BINS + s], L.xmax[s]);
+    atomicMax(&bins[3 * ADE_BINS + s], L.ymax[s]);
+    atomicAdd(&bins[4 * ADE_BINS + s], L.cnt[s]);
+  }
+}
+
+// Every workgroup ranks the 256 presence counts (thread t = B value t) and maps its share of the B plane in place;
+// workgroup 0 also writes the table rows and the status record.
+__global__ __launch_bounds__(256) void ade_rank_kernel(const int* __restrict__ bins, long long n, long long per, int vec,
+                                                       unsigned char* __restrict__ inst_out, int* __restrict__ status,
+                                                       int* __restrict__ table) {
+  __shared__ unsigned char rank[ADE_BINS];
+  __shared__ int wave_total[4];
+  const int t = threadIdx.x, lane = t & 63;
+  const int count = bins[4 * ADE_BINS + t];
+  const unsigned long long present = __ballot(count > 0);
+  if (lane == 0) wave_total[t >> 6] = __popcll(present);
+  __syncthreads();
+  int r = __popcll(present & ((1ull << lane) - 1ull)), total = 0;
+  for (int w = 0; w < 4; ++w) {
+    if (w < (t >> 6)) r += wave_total[w];
+    total += wave_total[w];
+  }
+  rank[t] = (unsigned char)r;                                  // read only where the value occurs
+  if (blockIdx.x == 0) {
+    if (count > 0) {
+      int* o = table + r * 7;
+      o[0] = r;
+      o[1] = t;
+      o[2] = bins[t];
+      o[3] = bins[ADE_BINS + t];
+      o[4] = bins[2 * ADE_BINS + t];
+      o[5] = bins[3 * ADE_BINS + t];
+      o[6] = count;
+    }
+    if (t == 0) {
+      status[0] = total;
+      status[1] = 0;
+    }
+  }
+  __syncthreads();
+  struct alignas(16) Q { unsigned char a[ADE_PX]; };
+  const long long groups = (n + ADE_PX - 1) / ADE_PX;
+  const long long g0 = blockIdx.x * per, g1 = g0 + per < groups ? g0 + per : groups;
+  for (long long g = g0 + t; g < g1; g += blockDim.x) {
+    const long long i0 = g * ADE_PX;
+    if (vec != 0 && i0 + ADE_PX <= n) {
+      Q q = *(const Q*)(inst_out + i0);
+#pragma unroll
+      for (int k = 0; k < ADE_PX; ++k) q.a[k] = rank[q.a[k]];
+      *(Q*)(inst_out + i0) = q;
+    } else {
+      for (int k = 0; k < ADE_PX && i0 + k < n; ++k) inst_out[i0 + k] = rank[inst_out[i0 + k]];
+    }
+  }
+}
+
 }  // namespace him
 
 using namespace him;
@@ -874,6 +1066,41 @@ int him_inst_summary(const void* inst, int inst_kind, const void* cls, int cls_k
   }
   hipLaunchKernelGGL(inst_median_kernel, dim3((max_objects + 3) / 4), dim3(256), 0, ST, hist, status, max_objects, table);
   return check_launch("inst_summary");
+}
+
+size_t him_ade_decode_workspace(void) { return ADE_WS_BYTES; }
+
+int him_ade_decode(const unsigned char* seg, int H, int W, int pixel_bytes, const unsigned short* keep, int n_keep,
+                   unsigned short* cls_out, unsigned char* label_out, unsigned char* inst_out, int* status, int* table,
+                   void* ws, size_t ws_bytes, void* stream) {
+  if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return fail(HIM_E_INVALID, "ade_decode: bad shape");
+  if (pixel_bytes != 3 && pixel_bytes != 4)
+    return fail(HIM_E_INVALID, "ade_decode: pixel_bytes %d (3 or 4)", pixel_bytes);
+  if (n_keep < 0 || n_keep > 255) return fail(HIM_E_INVALID, "ade_decode: n_keep %d (0..255)", n_keep);
+  if (!seg || (!keep && n_keep > 0) || !label_out || !inst_out || !status || !table || !ws)
+    return fail(HIM_E_INVALID, "ade_decode: null pointer");
+  if ((uintptr_t)ws % 16 != 0) return fail(HIM_E_INVALID, "ade_decode: workspace not 16-byte aligned");
+  if (ws_bytes < ADE_WS_BYTES)
+    return fail(HIM_E_INVALID, "ade_decode: workspace %zu < %zu bytes", ws_bytes, (size_t)ADE_WS_BYTES);
+  int* bins = (int*)ws;
+  unsigned char* lut = (unsigned char*)(bins + 5 * ADE_BINS);
+  const long long n = (long long)H * W, groups = (n + ADE_PX - 1) / ADE_PX;
+  long long blocks = (groups + 511) / 512;
+  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  const long long per = (groups + blocks - 1) / blocks;
+  const dim3 grid((unsigned)blocks);
+  // whole 16-byte words need every plane's base on a 16-byte boundary (groups are 48 / 64 bytes in, 16 / 32 bytes out)
+  const int vec = ((uintptr_t)seg % 16 == 0 && (uintptr_t)label_out % 16 == 0 && (uintptr_t)inst_out % 16 == 0 &&
+                   (uintptr_t)cls_out % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(ade_setup_kernel, dim3(1), dim3(256), 0, ST, keep, n_keep, bins, lut);
+  if (pixel_bytes == 3)
+    hipLaunchKernelGGL(ade_first_kernel<3>, grid, dim3(256), 0, ST, seg, H, W, vec, per, lut, cls_out, label_out,
+                       inst_out, bins);
+  else
+    hipLaunchKernelGGL(ade_first_kernel<4>, grid, dim3(256), 0, ST, seg, H, W, vec, per, lut, cls_out, label_out,
+                       inst_out, bins);
+  hipLaunchKernelGGL(ade_rank_kernel, grid, dim3(256), 0, ST, bins, n, per, vec, inst_out, status, table);
+  return check_launch("ade_decode");
 }
 
 }  // extern "C"

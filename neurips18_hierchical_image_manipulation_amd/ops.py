@@ -2397,3 +2397,95 @@ def inst_summary(inst, cls, min_id=1000, max_objects=1024):
         why = [text % dict(max=int(max_objects), count=count) for bit, text in _INST_FLAGS if flags & bit]
         raise ValueError('inst_summary: ' + '; '.join(why))
     return host[2:2 + 7 * count].reshape(count, 7).copy()
+
+
+# -- ADE20K segmentation decode: preprocess_ade's per-image work in one device call (include/him.h) ---------------------
+_ADE_STATE = {}         # device index -> workspace, status + table, pinned host copy, event, stream, keep tuple -> tensor
+
+
+def _ade_keep(keep):
+    """``keep`` as a tuple of ints, checked on the host.  Upstream relabels with one in-place rewrite per entry, in list
+    order; that equals a table lookup only when no entry repeats and none lies in 1..len(keep) (a position an earlier
+    rewrite produced would be rewritten again)."""
+    try:
+        ids = tuple(int(k) for k in keep)
+    except (TypeError, ValueError):
+        raise ValueError('ade_decode: keep must be a sequence of class ids')
+    if len(ids) > 255:
+        raise ValueError('ade_decode: keep has %d entries (at most 255)' % len(ids))
+    for k in ids:
+        if not 0 <= k <= 65535:
+            raise ValueError('ade_decode: keep entry %d outside 0..65535' % k)
+        if 1 <= k <= len(ids):
+            raise ValueError('ade_decode: keep entry %d lies in 1..%d, where upstream\'s sequential relabel is not a '
+                             'lookup' % (k, len(ids)))
+    if len(set(ids)) != len(ids):
+        raise ValueError('ade_decode: keep holds a duplicate entry')
+    return ids
+
+
+def _ade_seg(seg):
+    if not torch.is_tensor(seg) or not seg.is_cuda:
+        raise ValueError('ade_decode: seg must be a device tensor')
+    if seg.dtype != torch.uint8:
+        raise ValueError('ade_decode: seg is %s, accepted: torch.uint8' % seg.dtype)
+    if seg.dim() != 3 or seg.shape[2] not in (3, 4) or 0 in seg.shape or not seg.is_contiguous():
+        raise ValueError('ade_decode: seg must be a contiguous (H, W, 3 or 4) tensor, got %s' % (tuple(seg.shape),))
+    if seg.shape[0] * seg.shape[1] > 0x7fffffff:
+        raise ValueError('ade_decode: %d x %d pixels (at most 2^31 - 1)' % (seg.shape[0], seg.shape[1]))
+    return seg.detach()
+
+
+def ade_decode_launch(seg, keep, want_cls=False):
+    """Queue the decode of a (H, W, 3|4) uint8 device tensor on the current stream; returns ``(label, inst, cls or None,
+    state)``: fresh (H, W) device planes and the cached per-device state whose ``out`` tensor (2 status ints, then 256
+    rows of 7) the kernels fill.  No copy of results, no host synchronisation (``ade_decode`` adds both).  The state is
+    ONE per device: the next launch on that device overwrites ``out``, so status and table of a launch must be read (or
+    copied on the same stream) before the next one is queued -- two launches queued back to back leave the second image's
+    rows.  The planes are fresh tensors per launch and are not affected."""
+    ids = _ade_keep(keep)
+    seg = _ade_seg(seg)
+    H, W, pb = seg.shape
+    with torch.cuda.device(seg.device):
+        key = torch.cuda.current_device()
+        st = _ADE_STATE.get(key)
+        if st is None:
+            nws = int(lib.him_ade_decode_workspace())
+            st = _ADE_STATE[key] = dict(
+                ws=torch.empty(nws, dtype=torch.uint8, device=seg.device), nws=nws,
+                out=torch.empty(2 + 7 * 256, dtype=torch.int32, device=seg.device),
+                host=torch.empty(2 + 7 * 256, dtype=torch.int32, pin_memory=True),
+                event=torch.cuda.Event(), stream=None, keep={})
+        elif st['stream'] != _stream():
+            torch.cuda.current_stream().wait_event(st['event'])      # the previous user of this workspace, elsewhere
+        kdev = st['keep'].get(ids)
+        if kdev is None:
+            import numpy as np
+            kdev = st['keep'][ids] = torch.from_numpy(np.array(ids if ids else [0], dtype=np.uint16)).to(seg.device)
+        label = torch.empty((H, W), dtype=torch.uint8, device=seg.device)
+        inst = torch.empty((H, W), dtype=torch.uint8, device=seg.device)
+        cls = torch.empty((H, W), dtype=torch.uint16, device=seg.device) if want_cls else None
+        out = st['out']
+        lib.him_ade_decode(_p(seg), H, W, pb, _p(kdev), len(ids), _p(cls) if want_cls else 0, _p(label), _p(inst),
+                           _p(out), _p(out) + 8, _p(st['ws']), st['nws'], _stream())
+        st['stream'] = _stream()
+        st['event'].record(torch.cuda.current_stream())
+    return label, inst, cls, st
+
+
+def ade_decode(seg, keep, want_cls=False):
+    """``(label, inst, rows[, cls])`` of one ADE20K ``_seg.png`` held as a (H, W, 3|4) uint8 device tensor: ``label`` the
+    1-based position of the pixel's class ``(R // 10) * 256 + G`` in ``keep`` (0: not kept), ``inst`` the rank of its B
+    value among the image's distinct B values, both (H, W) uint8 device planes; ``rows`` an (n, 7) host ``int32`` array
+    ``rank, b, xmin, ymin, xmax, ymax, count`` (inclusive zero-based box), one row per B value in ascending rank; ``cls``
+    (``want_cls``) the raw classes as a uint16 device plane.  One asynchronous copy of status + table into a pinned buffer
+    and one wait on the current stream.  ``ValueError`` for a ``seg`` or a ``keep`` outside the contract."""
+    label, inst, cls, st = ade_decode_launch(seg, keep, want_cls)
+    with torch.cuda.device(st['out'].device):
+        st['host'].copy_(st['out'], non_blocking=True)
+        st['event'].record(torch.cuda.current_stream())
+        torch.cuda.current_stream().synchronize()
+    host = st['host'].numpy()
+    count = int(host[0])
+    rows = host[2:2 + 7 * count].reshape(count, 7).copy()
+    return (label, inst, rows, cls) if want_cls else (label, inst, rows)
