@@ -628,6 +628,72 @@ int him_ade_decode(const unsigned char* seg, int H, int W, int pixel_bytes, cons
                    unsigned short* cls_out, unsigned char* label_out, unsigned char* inst_out, int* status, int* table,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation metrics (the reference ships none; these are the measures this line of work reports): SSIM / PSNR / L1
+ * sums of a generated batch against the real one inside the edited box, and the confusion matrix behind pixel
+ * accuracy, class IoU and object-mask IoU.  One call each on `stream`, no host synchronisation, results bit-identical
+ * from run to run.
+ *
+ * him_image_metrics: a, b (B,C,H,W) planar fp32, C = 1 or 3, never written.
+ *   Mapping on load: x' = x * scale + offset, the product and the sum each rounded to fp32; with quantize != 0 then
+ *   x' = trunc(clip(x', 0, 255)).  ONE preset takes another operation order: scale = 127.5, offset = 127.5 and
+ *   quantize != 0 evaluates (x + 1) / 2 * 255 as him_tensor2im_bytes(normalize = 1) does, so that the values are the
+ *   bytes of the saved pictures and the SSIM is theirs.
+ *   SSIM (Wang et al. 2004): separable 11 x 11 window, g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), i = 0..10, normalised to
+ *   sum 1 in double and then rounded to fp32; only windows wholly inside the image (or the box) are used, so the map is
+ *   (H - 10) x (W - 10); weighted moments mu_a, mu_b, E[a^2], E[b^2], E[ab]; s_a^2 = E[a^2] - mu_a^2, s_b^2 likewise,
+ *   s_ab = E[ab] - mu_a mu_b, no sample correction; C1 = (0.01 L)^2, C2 = (0.03 L)^2 with L = data_range (computed in
+ *   double, rounded to fp32);
+ *     ssim = (2 mu_a mu_b + C1) (2 s_ab + C2) / ((mu_a^2 + mu_b^2 + C1) (s_a^2 + s_b^2 + C2)).
+ *   The moments are accumulated in fp32 on x' - p with a per-tile pivot p (the tile's first pixel; variance and covariance
+ *   are shift-invariant, the means get p back), which avoids the cancellation of E[x^2] - mu^2 on bright flat regions.
+ *   box:  NULL = the whole image; else (B,4) int32 on the device, (xmin, ymin, xmax, ymax) inclusive, clipped to the
+ *         image.  Everything is evaluated as if both images had been cropped to the box.  A box thinner than 11 in
+ *         either direction has 0 windows (its error sums are still produced); an empty box gives five zeros.
+ *   sums: (B,C,5) doubles per plane: [sum of ssim over the windows, number of windows, sum of (a' - b')^2, sum of
+ *         |a' - b'|, number of pixels].  The error sums are accumulated in double.
+ *   map_out: NULL, or (B,C,H-10,W-10) fp32, the SSIM of every window; whole-image calls only (box must be NULL, H and
+ *         W >= 11).  `sums` does not depend on whether the map is written.
+ *   ws:   him_image_metrics_workspace(B, C, H, W) bytes, 8-byte aligned, fully overwritten by the call.
+ *   Limits: H * W <= 2^31 - 1, B * C <= 65535 planes, H <= 65535 * 16 rows; beyond them the call is refused.
+ *   Kernel layout: one 256-thread workgroup per tile of 16 x 64 window origins stages (16+10) x (64+10) pixels of both
+ *   images in LDS once, runs the row pass into LDS and the column pass from it, and writes three doubles to its own
+ *   workspace slot; a second launch adds a plane's slots in a fixed order in double.  No floating-point atomics.
+ *
+ * him_confusion: counts[gt id][predicted id] over the pixels of a batch of label planes, in integers.
+ *   pred: pred_kind 0 uint8 ids / 1 int32 ids / 2 int64 ids / 3 fp32 holding integral ids, all (B,1,H,W) with C = 1;
+ *         4 fp32 scores (B,C,H,W), the label is the channel of the maximum, the lowest channel on a tie (strict >
+ *         walking upwards, him_label2color_bytes' rule); 5 fp32 probabilities (B,1,H,W), C = 1, label = p > 0.5 ? 1 : 0
+ *         (the reference's object-mask threshold, models/TwoStreamAE_mask.py:333).
+ *   gt:   gt_kind 0..3 as pred_kind 0..3, (B,1,H,W).
+ *   mask: NULL, or fp32 (B,1,H,W): a pixel counts where mask != 0.
+ *   ignore: a ground-truth id whose pixels are left out (compared before the range check, so it may be >= n); -1: none.
+ *   n:    classes, 1 <= n <= 256.  A pixel that passes mask and ignore and whose gt or predicted id is negative, >= n or
+ *         a non-integral fp32 is SKIPPED: it is counted in status[0] and never in counts.
+ *   counts: int64, (B,n,n) with per_sample != 0, else (1,n,n); row = ground truth, column = prediction.
+ *   accumulate != 0 adds into counts and into status (status[0] += skipped, flags are or-ed): an evaluation loop needs
+ *         neither a host add nor a synchronisation.  Otherwise both are overwritten.
+ *   status: 2 ints: [0] = skipped pixels (saturating at 2^31 - 1), [1] = HIM_CONF_SKIPPED | HIM_CONF_SATURATED bits.
+ *   ws:   him_confusion_workspace(n) bytes, 8-byte aligned, cleared by the call itself.
+ *   Each workgroup keeps a private 32-bit histogram in LDS while n <= 160 (n * n * 4 bytes <= 100 KiB of the CU's 160
+ *   KiB; a workgroup's share of pixels stays below 2^32) and flushes its non-zero cells with 64-bit integer atomics;
+ *   above that it adds to counts directly.  Integer adds commute: exact, and identical from run to run.  Planes whose
+ *   base is not 16-byte aligned or whose width is not a multiple of 4 are read element by element.  H * W <= 2^31 - 1.
+ *   Nothing outside counts, status and ws is written.
+ * Both return HIM_E_INVALID / HIM_E_WORKSPACE before any launch for a NULL required pointer, C outside {1, 3} (image
+ * metrics), H or W < 1, n out of range, an unknown kind, or a workspace smaller than the query's size.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_CONF_SKIPPED 1
+#define HIM_CONF_SATURATED 2
+size_t him_image_metrics_workspace(int B, int C, int H, int W);
+int him_image_metrics(const float* a, const float* b, int B, int C, int H, int W, float scale, float offset, int quantize,
+                      float data_range, const int* box, double* sums, float* map_out, void* ws, size_t ws_bytes,
+                      void* stream);
+size_t him_confusion_workspace(int n);
+int him_confusion(const void* pred, int pred_kind, const void* gt, int gt_kind, const float* mask, int B, int C, int H,
+                  int W, int n, int ignore, int per_sample, int accumulate, long long* counts, int* status, void* ws,
+                  size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

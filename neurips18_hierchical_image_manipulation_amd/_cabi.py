@@ -140,6 +140,11 @@ _SIGS = {
     'him_inst_summary': (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     'him_ade_decode_workspace': (c_size_t, []),
     'him_ade_decode': (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, c_size_t, P]),
+    'him_image_metrics_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'him_image_metrics': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_float, P, P, P, P, c_size_t, P]),
+    'him_confusion_workspace': (c_size_t, [c_int]),
+    'him_confusion': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P,
+                              c_size_t, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

@@ -2489,3 +2489,122 @@ def ade_decode(seg, keep, want_cls=False):
     count = int(host[0])
     rows = host[2:2 + 7 * count].reshape(count, 7).copy()
     return (label, inst, rows, cls) if want_cls else (label, inst, rows)
+
+
+# -- evaluation metrics: SSIM / error sums and the confusion matrix in one device call each (include/him.h) -------------
+_MET_WS = {}            # (B, C, H, W, device index) -> workspace of him_image_metrics
+_CONF_WS = {}           # (n, device index) -> workspace of him_confusion
+_PRED_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
+CONF_SKIPPED, CONF_SATURATED = 1, 2
+
+
+def _metric_image(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('image_metrics: %s must be a device tensor' % what)
+    if t.dtype != torch.float32:
+        raise ValueError('image_metrics: %s is %s, accepted: torch.float32' % (what, t.dtype))
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[1] not in (1, 3) or 0 in t.shape:
+        raise ValueError('image_metrics: %s must be (B, 1 or 3, H, W), got %s' % (what, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def image_metrics(a, b, *, scale, offset, quantize, data_range, box=None, want_map=False):
+    """``(sums, map)`` of two (B, C, H, W) fp32 device batches, C = 1 or 3: ``sums`` (B, C, 5) float64 on the device =
+    [sum of SSIM over the windows, windows, sum of squared error, sum of absolute error, pixels] per plane after the
+    mapping ``x * scale + offset`` (and ``trunc(clip(., 0, 255))`` with ``quantize``); ``map`` the (B, C, H-10, W-10)
+    SSIM map with ``want_map`` (whole-image calls only), else None.  ``box``: (B, 4) int32 device tensor of inclusive
+    ``(xmin, ymin, xmax, ymax)``, or None.  Current stream, no host synchronisation.  The workspace is cached per shape
+    and device and is not guarded by events: calls of one shape must be queued on one stream at a time."""
+    a, b = _metric_image(a, 'a'), _metric_image(b, 'b')
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError('image_metrics: a %s on %s and b %s on %s differ' % (tuple(a.shape), a.device, tuple(b.shape),
+                                                                              b.device))
+    B, C, H, W = a.shape
+    if box is not None:
+        if not torch.is_tensor(box) or not box.is_cuda or box.dtype != torch.int32 or tuple(box.shape) != (B, 4):
+            raise ValueError('image_metrics: box must be a (%d, 4) int32 device tensor' % B)
+        if want_map:
+            raise ValueError('image_metrics: the map is written for whole-image calls only')
+        box = box.contiguous()
+    if want_map and (H < 11 or W < 11):
+        raise ValueError('image_metrics: no 11x11 window fits a %dx%d image' % (H, W))
+    with torch.cuda.device(a.device):
+        key = (B, C, H, W, torch.cuda.current_device())
+        ws = _MET_WS.get(key)
+        if ws is None:
+            ws = _MET_WS[key] = torch.empty(max(int(lib.him_image_metrics_workspace(B, C, H, W)) // 8, 1),
+                                            dtype=torch.float64, device=a.device)
+        sums = torch.empty((B, C, 5), dtype=torch.float64, device=a.device)
+        smap = torch.empty((B, C, H - 10, W - 10), dtype=torch.float32, device=a.device) if want_map else None
+        lib.him_image_metrics(_p(a), _p(b), B, C, H, W, float(scale), float(offset), 1 if quantize else 0,
+                              float(data_range), _p(box), _p(sums), _p(smap), _p(ws), ws.numel() * 8, _stream())
+    return sums, smap
+
+
+def _label_planes(t, what, kinds, scores=False):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('confusion: %s must be a device tensor' % what)
+    if t.dtype not in kinds:
+        raise ValueError('confusion: %s is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in kinds)))
+    if t.dim() == 2:
+        t = t[None, None]
+    elif t.dim() == 3:
+        t = t.unsqueeze(1)
+    if t.dim() != 4 or 0 in t.shape or (t.shape[1] != 1 and not scores):
+        raise ValueError('confusion: %s must be (B, 1, H, W), (B, H, W) or (H, W), got %s' % (what, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, pred_kind=None):
+    """``(counts, status)``: the int64 confusion matrix (B or 1, n, n) of ``pred`` against ``gt`` (row = ground truth,
+    column = prediction) and the 2-int status record (skipped pixels, flag bits), both on the device.  ``pred``: uint8 /
+    int32 / int64 / integral fp32 ids, or fp32 scores (B, C > 1, H, W) (arg-max, lowest channel on a tie), or with
+    ``pred_kind='prob'`` fp32 probabilities thresholded at 0.5.  ``mask``: fp32, pixels count where it is not 0.
+    ``out``: the pair an earlier call returned; the call then adds into it.  Current stream, no host synchronisation.  The
+    workspace is cached per ``n`` and device: calls with one ``n`` must be queued on one stream at a time."""
+    gt = _label_planes(gt, 'gt', _PRED_KINDS)
+    pred = _label_planes(pred, 'pred', _PRED_KINDS, scores=True)
+    if pred_kind == 'prob':
+        kind = 5
+    elif pred_kind == 'scores' or (pred_kind is None and pred.dtype == torch.float32 and pred.shape[1] > 1):
+        kind = 4
+    elif pred_kind in (None, 'ids'):
+        kind = _PRED_KINDS[pred.dtype]
+    else:
+        raise ValueError("confusion: pred_kind %r (None, 'ids', 'scores' or 'prob')" % (pred_kind,))
+    if kind in (4, 5) and pred.dtype != torch.float32:
+        raise ValueError('confusion: scores and probabilities are fp32, got %s' % pred.dtype)
+    if kind != 4 and pred.shape[1] != 1:
+        raise ValueError('confusion: id / probability planes have one channel, got %s' % (tuple(pred.shape),))
+    B, C, H, W = pred.shape
+    if tuple(gt.shape) != (B, 1, H, W) or gt.device != pred.device:
+        raise ValueError('confusion: pred %s and gt %s differ' % (tuple(pred.shape), tuple(gt.shape)))
+    if mask is not None:
+        mask = _label_planes(mask, 'mask', (torch.float32,))
+        if tuple(mask.shape) != (B, 1, H, W) or mask.device != pred.device:
+            raise ValueError('confusion: mask %s does not fit pred %s' % (tuple(mask.shape), tuple(pred.shape)))
+    n = int(n)
+    if not 1 <= n <= 256:
+        raise ValueError('confusion: n must be in 1..256, got %d' % n)
+    rows = B if per_sample else 1
+    with torch.cuda.device(pred.device):
+        key = (n, torch.cuda.current_device())
+        ws = _CONF_WS.get(key)
+        if ws is None:
+            ws = _CONF_WS[key] = torch.empty(max(int(lib.him_confusion_workspace(n)) // 8, 1), dtype=torch.int64,
+                                             device=pred.device)
+        if out is None:
+            counts = torch.empty((rows, n, n), dtype=torch.int64, device=pred.device)
+            status = torch.empty(2, dtype=torch.int32, device=pred.device)
+        else:
+            counts, status = out
+            if counts.dtype != torch.int64 or tuple(counts.shape) != (rows, n, n) or not counts.is_contiguous() \
+                    or counts.device != pred.device or status.dtype != torch.int32 or status.numel() != 2:
+                raise ValueError('confusion: out must be the (counts (%d, %d, %d) int64, status (2,) int32) pair of an '
+                                 'earlier call' % (rows, n, n))
+        lib.him_confusion(_p(pred), kind, _p(gt), _PRED_KINDS[gt.dtype], _p(mask), B, C, H, W, n, int(ignore),
+                          1 if per_sample else 0, 0 if out is None else 1, _p(counts), _p(status), _p(ws),
+                          ws.numel() * 8, _stream())
+    return counts, status

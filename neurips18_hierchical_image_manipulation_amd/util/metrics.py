@@ -1,0 +1,240 @@
+"""Evaluation metrics on the device: SSIM / PSNR / L1 of a generated image against the real one (inside the edited box),
+pixel accuracy and IoU of a predicted layout, IoU of a generated object mask.  The reference ships no metric code; the
+definitions are those of include/him.h "Evaluation metrics".  Every function queues device work on the current stream
+and returns device tensors; nothing synchronises with the host before ``Evaluator.summary()`` as long as every argument
+is a device tensor: a ``box`` given as a list or array (and any host tensor) is copied to the device first, which waits
+on the host.  The device calls share one cached workspace per shape and device (``ops.image_metrics`` /
+``ops.confusion``): calls of one shape must be queued on one stream at a time."""
+import json
+import math
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from .. import ops
+
+
+def _mapping(data_range, as_bytes):
+    """``as_bytes``: the inputs are generator-range tensors in [-1, 1] and are compared as the bytes ``tensor2im`` saves
+    (the preset of him_image_metrics); otherwise they are compared as they stand."""
+    if as_bytes:
+        return dict(scale=127.5, offset=127.5, quantize=True, data_range=float(data_range))
+    return dict(scale=1.0, offset=0.0, quantize=False, data_range=float(data_range))
+
+
+def _box(box, B, device):
+    """None, or a (B, 4) int32 device tensor of inclusive (xmin, ymin, xmax, ymax) from a tensor / array / sequence.  Only
+    a device tensor passes without a host-to-device copy (a pageable copy synchronises with the host)."""
+    if box is None:
+        return None
+    if not torch.is_tensor(box):
+        box = torch.from_numpy(np.asarray(box, dtype=np.int32).reshape(-1, 4))
+    box = box.reshape(-1, 4).to(device=device, dtype=torch.int32, non_blocking=True)
+    if box.shape[0] == 1 and B > 1:
+        box = box.expand(B, 4)
+    return box.contiguous()
+
+
+def _image_pair(a, b):
+    a = a if a.dim() == 4 else a.unsqueeze(0)
+    b = b if b.dim() == 4 else b.unsqueeze(0)
+    if not a.is_cuda:
+        a = a.cuda()
+    return a.float(), b.to(a.device).float()
+
+
+def image_sums(a, b, data_range=255., as_bytes=True, box=None, want_map=False):
+    """The raw (B, C, 5) float64 device sums of ``ops.image_metrics`` (and the SSIM map or None)."""
+    a, b = _image_pair(a, b)
+    return ops.image_metrics(a, b, box=_box(box, a.shape[0], a.device), want_map=want_map, **_mapping(data_range, as_bytes))
+
+
+def _ratio(sums, num, den):
+    return sums[:, :, num].sum(1) / sums[:, :, den].sum(1)          # 0 / 0 = nan: no window / no pixel
+
+
+def ssim(a, b, data_range=255., as_bytes=True, box=None, return_map=False):
+    """Per-image SSIM (B,) float64 on the device, the mean over channels and windows; nan where no 11 x 11 window fits.
+    With ``return_map`` also the (B, C, H-10, W-10) map (whole images only)."""
+    sums, smap = image_sums(a, b, data_range, as_bytes, box, return_map)
+    out = _ratio(sums, 0, 1)
+    return (out, smap) if return_map else out
+
+
+def psnr(a, b, data_range=255., as_bytes=True, box=None):
+    """Per-image 10 log10(L^2 / MSE) (B,) float64 on the device; inf for identical images, nan for an empty box."""
+    sums, _ = image_sums(a, b, data_range, as_bytes, box)
+    return 10.0 * torch.log10(float(data_range) ** 2 / _ratio(sums, 2, 4))
+
+
+def l1(a, b, data_range=255., as_bytes=True, box=None):
+    """Per-image mean absolute error (B,) float64 on the device, in the units of the mapped values."""
+    sums, _ = image_sums(a, b, data_range, as_bytes, box)
+    return _ratio(sums, 3, 4)
+
+
+def _labels(t, keys):
+    """What the models hand out: a tensor, a dict of generate() / reconstruct(), or the 3-tuple of gen_layout()."""
+    if isinstance(t, dict):
+        for k in keys:
+            if k in t:
+                return t[k]
+        raise KeyError('none of %s in %s' % (keys, sorted(t)))
+    if isinstance(t, (tuple, list)):
+        return t[-1]
+    return t
+
+
+def _plane(t):
+    if not t.is_cuda:
+        t = t.cuda()
+    if t.dtype not in (torch.uint8, torch.int32, torch.int64, torch.float32):
+        t = t.float()
+    return t
+
+
+def confusion_matrix(pred, gt, n_class, mask=None, ignore_label=None, per_sample=False, out=None, pred_kind=None):
+    """``(counts, status)`` on the device: int64 (B or 1, n_class, n_class), row = ground truth, column = prediction, and
+    the status record of ``ops.confusion``.  ``pred``: ids, or (B, C > 1, H, W) scores; ``out`` accumulates."""
+    pred = _plane(_labels(pred, ('comb_pred_label', 'comb_recon_label')))
+    gt = _plane(gt).to(pred.device)
+    if mask is not None:
+        mask = mask.to(pred.device).float()
+    return ops.confusion(pred, gt, n_class, mask=mask, ignore=-1 if ignore_label is None else int(ignore_label),
+                         per_sample=per_sample, out=out, pred_kind=pred_kind)
+
+
+def segmentation_scores(conf):
+    """pixel_acc, mean_acc, mean_iou, fw_iou, per_class_iou, per_class_acc and n_absent of an (n, n) (or (1, n, n))
+    confusion matrix, in float64 on the host.  Classes absent from both prediction and ground truth are left out of the
+    means (their per-class entries are nan) and counted in ``n_absent``."""
+    c = conf.detach().cpu().numpy() if torch.is_tensor(conf) else np.asarray(conf)
+    c = c.reshape(c.shape[-2], c.shape[-1]).astype(np.float64)
+    tp, n_gt, n_pred, total = np.diagonal(c), c.sum(axis=1), c.sum(axis=0), float(c.sum())
+    union = n_gt + n_pred - tp
+    seen, has_gt = (n_gt + n_pred) > 0, n_gt > 0
+    iou = np.full(len(tp), np.nan)
+    acc = np.full(len(tp), np.nan)
+    iou[seen] = tp[seen] / union[seen]
+    acc[has_gt] = tp[has_gt] / n_gt[has_gt]
+    nan = float('nan')
+    return OrderedDict([
+        ('pixel_acc', float(tp.sum()) / total if total > 0 else nan),
+        ('mean_acc', float(acc[has_gt].mean()) if has_gt.any() else nan),
+        ('mean_iou', float(iou[seen].mean()) if seen.any() else nan),
+        ('fw_iou', float((n_gt[has_gt] * iou[has_gt]).sum()) / total if total > 0 else nan),
+        ('per_class_iou', iou), ('per_class_acc', acc), ('n_absent', int((~seen).sum()))])
+
+
+def mask_iou(prob, gt_mask):
+    """Per-sample intersection over union (B,) float64 on the device of ``prob > 0.5`` against ``gt_mask`` (0 / 1), from
+    the n = 2 per-sample confusion matrix; nan where both are empty."""
+    prob = _plane(_labels(prob, ('obj_pred_label', 'obj_recon_label'))).float()
+    counts, _ = ops.confusion(prob, _plane(gt_mask).to(prob.device), 2, per_sample=True, pred_kind='prob')
+    c = counts.double()
+    return c[:, 1, 1] / (c[:, 1, 1] + c[:, 0, 1] + c[:, 1, 0])
+
+
+def box_of_mask(mask):
+    """(B, 4) int32 device tensor: the inclusive extent (xmin, ymin, xmax, ymax) of the non-zero pixels of a (B, 1, H, W)
+    mask; an all-zero mask gives an empty box.  Device reductions only, no host synchronisation."""
+    m = (mask.reshape(mask.shape[0], mask.shape[-2], mask.shape[-1]) != 0)
+    rows, cols = m.any(2).int(), m.any(1).int()
+    H, W = rows.shape[1], cols.shape[1]
+    none = rows.sum(1) == 0
+    ymin, xmin = rows.argmax(1), cols.argmax(1)
+    ymax, xmax = H - 1 - rows.flip(1).argmax(1), W - 1 - cols.flip(1).argmax(1)
+    box = torch.stack([xmin, ymin, xmax, ymax], 1)
+    return torch.where(none[:, None], -1, box).to(torch.int32).contiguous()        # (-1, -1, -1, -1) clips to nothing
+
+
+SUMMARY_KEYS = ('n_images', 'ssim', 'psnr', 'l1', 'n_layouts', 'pixel_acc', 'mean_acc', 'mean_iou', 'fw_iou',
+                'per_class_iou', 'per_class_acc', 'n_absent', 'skipped_pixels', 'n_object_masks', 'mask_iou')
+
+
+class Evaluator(object):
+    """Accumulates the three groups of measures on the device: ``add_image`` (SSIM / PSNR / L1 per image, as the bytes
+    ``tensor2im`` saves), ``add_layout`` (one pooled ``label_nc`` x ``label_nc`` confusion matrix), ``add_object_mask``
+    (IoU per sample).  It takes what ``Pix2PixHDModel_condImg.inference``, ``TwoStreamAE_mask.evaluate`` / ``generate`` /
+    ``reconstruct`` and ``JointInference.gen_layout`` / ``gen_image`` return (a tensor, their dict, or their tuple, whose
+    last entry is the generated tensor).  Nothing crosses to the host before ``summary()``."""
+
+    def __init__(self, label_nc, data_range=255., as_bytes=True):
+        self.label_nc, self.data_range, self.as_bytes = int(label_nc), float(data_range), bool(as_bytes)
+        self._image, self._conf, self._mask, self._layouts = [], None, [], 0
+
+    def add_image(self, fake, real, box=None):
+        fake = _labels(fake, ('fake_image',))
+        sums, _ = image_sums(fake, real, self.data_range, self.as_bytes, box)
+        self._image.append(sums.sum(1))                               # (B, 5): channels pooled
+        return self
+
+    def add_layout(self, pred, gt, mask=None):
+        if self._conf is None:
+            pred_t = _plane(_labels(pred, ('comb_pred_label', 'comb_recon_label')))
+            with torch.cuda.device(pred_t.device):
+                self._conf = (torch.zeros((1, self.label_nc, self.label_nc), dtype=torch.int64, device=pred_t.device),
+                              torch.zeros(2, dtype=torch.int32, device=pred_t.device))
+        confusion_matrix(pred, gt, self.label_nc, mask=mask, out=self._conf)
+        self._layouts += 1
+        return self
+
+    def add_object_mask(self, prob, gt):
+        self._mask.append(mask_iou(prob, gt))
+        return self
+
+    def summary(self):
+        """The measures so far as plain python values (the one host synchronisation)."""
+        nan = float('nan')
+        out = OrderedDict((k, nan) for k in SUMMARY_KEYS)
+        out.update(n_images=0, n_layouts=0, n_object_masks=0, n_absent=0, skipped_pixels=0, per_class_iou=[],
+                   per_class_acc=[])
+        if self._image:
+            s = torch.cat(self._image, 0).cpu().numpy()
+            with np.errstate(divide='ignore', invalid='ignore'):
+                per_ssim, mse, mae = s[:, 0] / s[:, 1], s[:, 2] / s[:, 4], s[:, 3] / s[:, 4]
+                per_psnr = 10.0 * np.log10(self.data_range ** 2 / mse)
+            out.update(n_images=int(len(s)), ssim=_nanmean(per_ssim), psnr=_nanmean(per_psnr), l1=_nanmean(mae))
+        if self._conf is not None:
+            sc = segmentation_scores(self._conf[0])
+            status = self._conf[1].cpu().numpy()
+            sc['per_class_iou'] = [None if math.isnan(v) else float(v) for v in sc['per_class_iou']]
+            sc['per_class_acc'] = [None if math.isnan(v) else float(v) for v in sc['per_class_acc']]
+            out.update(sc)
+            out.update(n_layouts=int(self._layouts), skipped_pixels=int(status[0]))
+        if self._mask:
+            m = torch.cat(self._mask, 0).cpu().numpy()
+            out.update(n_object_masks=int(len(m)), mask_iou=_nanmean(m))
+        return out
+
+    def write_json(self, path):
+        with open(path, 'w') as f:
+            json.dump({k: (None if isinstance(v, float) and not math.isfinite(v) else v)
+                       for k, v in self.summary().items()}, f, indent=1)
+        return path
+
+
+def _nanmean(v):
+    v = np.asarray(v, np.float64)
+    keep = ~np.isnan(v)
+    return float(v[keep].mean()) if keep.any() else float('nan')
+
+
+def evaluate_mask2image(model, dataset, how_many, evaluator=None):
+    """The loop of the reference's vis_mask2image.py (``model.inference`` per sample of ``dataset``, batch 1, the first
+    ``how_many`` samples) feeding an ``Evaluator``: generated against real image inside the edited box.  The box is the
+    loader's ``input_bbox`` when the sample carries one, else the extent of ``mask_in``.  Returns the evaluator."""
+    ev = evaluator if evaluator is not None else Evaluator(getattr(model.opt, 'label_nc', 35))
+    for i, data in enumerate(dataset):
+        if i >= how_many:
+            break
+        fake = model.inference(label=data['label'], inst=data['inst'], image=data['image'], mask_in=data['mask_in'],
+                               mask_out=data['mask_out'])
+        if 'input_bbox' in data:      # the loader's (wmin, hmin, wmax, hmax), the far edges exclusive
+            box = torch.as_tensor(data['input_bbox']).reshape(-1, 4).to(fake.device, torch.int32).clone()
+            box[:, 2:] -= 1
+        else:
+            box = box_of_mask(data['mask_in'].to(fake.device))
+        ev.add_image(fake, data['image'], box=box)
+    return ev
