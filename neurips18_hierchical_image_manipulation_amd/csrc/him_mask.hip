@@ -34,23 +34,63 @@ __device__ __forceinline__ float act_grad_from_z(float z, int act, float slope) 
 }
 
 // ---- BatchNorm2d ------------------------------------------------------------------------------------------------
-// partial[(c*S + s)*2 + {0,1}] = sum, sum of squares of (x - shift_c) over slice s of channel c; shift_c = x[0][c][0].
-// A slice is a contiguous range of the channel's B*hw positions; inside one image plane the run is contiguous in memory
-// (float4 loads when hw % 4 == 0), so no per-element division.
+// Slice s of BN_SLICES over the n = B*hw positions of one channel; with hw % 4 == 0 the bounds fall on multiples of 4.
+// (BN_SLICES is a power of two: the bounds are shifts, which bn_finalize_kernel computes 32 times per channel.)
+__device__ __forceinline__ void bn_slice(long long n, int s, bool vec, long long* lo, long long* hi) {
+  long long l = n * s / BN_SLICES, h = n * (s + 1) / BN_SLICES;
+  if (vec) {
+    l &= ~3ll;
+    h = (s == BN_SLICES - 1) ? n : (h & ~3ll);
+  }
+  *lo = l;
+  *hi = h;
+}
+
+// partial[(c*S + s)*3 + {0,1,2}] = pivot, mean - pivot, sum of squared deviations from the mean (M2) over slice s of
+// channel c; the mean stays in two parts so that a channel with |mean| >> deviation loses nothing to its rounding.
+// The sums run over x - pivot with the slice's OWN pivot: the average of its first 1024 elements (256 on the scalar
+// path), which every thread loads anyway as its first element(s) -- the pivot costs one block reduction and no memory
+// traffic.  For any data (pivot - slice mean)^2 <= (slice length / sample size) * slice variance, so q - a*a/len below
+// loses a bounded number of bits whatever the data, and close to none when the head of a slice looks like the rest; one
+// outlier cannot drag the pivot away from the bulk (as a pivot x[0][c][0] could), and a common offset of the whole
+// channel drops out as before.  A slice is a contiguous range of the channel's B*hw positions; inside one image plane
+// the run is contiguous in memory (float4 loads when hw % 4 == 0), so no per-element division.
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, float* __restrict__ partial, int B, int C,
                                                        int hw) {
   __shared__ float sh[8];
-  const int c = blockIdx.x, s = blockIdx.y, S = gridDim.y;
+  const int c = blockIdx.x, s = blockIdx.y, S = BN_SLICES;  // launched with gridDim.y == BN_SLICES
   const long long n = (long long)B * hw;
-  long long lo = n * s / S, hi = n * (s + 1) / S;
   const bool vec = (hw & 3) == 0;
-  if (vec) {
-    lo &= ~3ll;
-    hi = (s == S - 1) ? n : (hi & ~3ll);
+  long long lo, hi;
+  bn_slice(n, s, vec, &lo, &hi);
+  if (hi <= lo) {  // fewer positions than slices: bn_finalize_kernel skips the slice
+    if (threadIdx.x < 3) partial[((size_t)c * S + s) * 3 + threadIdx.x] = 0.f;
+    return;
   }
-  const float shift = x[(size_t)c * hw];
+  const int per = vec ? 4 : 1;
+  const long long head = min(hi - lo, (long long)256 * per);  // pivot sample and first chunk of the data in one load
+  const bool has = (long long)threadIdx.x * per < head;
+  float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (has) {
+    const long long p = lo + (long long)threadIdx.x * per;
+    const int b = (int)(p / hw), r = (int)(p - (long long)b * hw);
+    const float* __restrict__ sp = x + ((size_t)b * C + c) * hw + r;
+    if (vec) hv = *(const float4*)sp;
+    else hv.x = *sp;
+  }
+  const float shift = block_sum_256((hv.x + hv.y) + (hv.z + hv.w), sh) / (float)head;
   float a = 0.f, q = 0.f;
-  for (long long p0 = lo; p0 < hi;) {
+  if (has) {
+    const float d0 = hv.x - shift, d1 = hv.y - shift, d2 = hv.z - shift, d3 = hv.w - shift;
+    if (vec) {
+      a = (d0 + d1) + (d2 + d3);
+      q = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    } else {
+      a = d0;
+      q = d0 * d0;
+    }
+  }
+  for (long long p0 = lo + head; p0 < hi;) {
     const int b = (int)(p0 / hw), r0 = (int)(p0 - (long long)b * hw);
     const int r1 = (int)min((long long)hw, r0 + (hi - p0));
     const float* __restrict__ pl = x + ((size_t)b * C + c) * hw;
@@ -73,16 +113,21 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   a = block_sum_256(a, sh);
   q = block_sum_256(q, sh);
   if (threadIdx.x == 0) {
-    partial[((size_t)c * S + s) * 2] = a;
-    partial[((size_t)c * S + s) * 2 + 1] = q;
+    const float ma = a / (float)(hi - lo);
+    partial[((size_t)c * S + s) * 3] = shift;
+    partial[((size_t)c * S + s) * 3 + 1] = ma;
+    partial[((size_t)c * S + s) * 3 + 2] = fmaxf(q - a * ma, 0.f);
   }
 }
 
 // mean / rstd of the batch (training) or from the running statistics (eval); training also updates the running
-// statistics the way torch does (momentum m, unbiased variance)
-__global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ partial, float* __restrict__ mean,
-                                   float* __restrict__ rstd, float* __restrict__ run_mean, float* __restrict__ run_var,
-                                   int B, int C, int hw, int S, float eps, float momentum, int training) {
+// statistics the way torch does (momentum m, unbiased variance).  The slices' (count, mean, M2) are merged in slice
+// order (Chan et al.): with e_s = mean_s - P (P = the average of the slices' pivots: a value next to the mean, so e_s is
+// of the size of the deviation and mean - P is small against the mean's own rounding), mean = P + sum n_s e_s / n and
+// M2 = sum M2_s + n_s (mean_s - mean)^2: nothing is ever taken as a difference of two large sums.
+__global__ void bn_finalize_kernel(const float* __restrict__ partial, float* __restrict__ mean, float* __restrict__ rstd,
+                                   float* __restrict__ run_mean, float* __restrict__ run_var, int B, int C, int hw,
+                                   float eps, float momentum, int training) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   if (!training) {
@@ -90,15 +135,40 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __r
     rstd[c] = 1.f / sqrtf(run_var[c] + eps);
     return;
   }
-  float a = 0.f, q = 0.f;
-  for (int s = 0; s < S; ++s) {
-    a += partial[((size_t)c * S + s) * 2];
-    q += partial[((size_t)c * S + s) * 2 + 1];
-  }
+  const long long nn = (long long)B * hw;
+  const bool vec = (hw & 3) == 0;
   const float n = (float)B * (float)hw;
-  const float ms = a / n;
-  const float mu = x[(size_t)c * hw] + ms;
-  const float var = fmaxf(q / n - ms * ms, 0.f);
+  const float* __restrict__ pc = partial + (size_t)c * BN_SLICES * 3;
+  float cnt[BN_SLICES], e[BN_SLICES], q[BN_SLICES];  // count, pivot (then mean - P), M2 of every slice, in registers
+  float P = 0.f, used = 0.f;
+#pragma unroll
+  for (int s = 0; s < BN_SLICES; ++s) {
+    long long lo, hi;
+    bn_slice(nn, s, vec, &lo, &hi);
+    cnt[s] = (float)(hi - lo);
+    e[s] = pc[s * 3];
+    q[s] = pc[s * 3 + 2];
+    if (cnt[s] > 0.f) {
+      P += e[s];
+      used += 1.f;
+    }
+  }
+  P /= used;
+  float am = 0.f;
+#pragma unroll
+  for (int s = 0; s < BN_SLICES; ++s) {
+    e[s] = (e[s] - P) + pc[s * 3 + 1];
+    if (cnt[s] > 0.f) am += cnt[s] * e[s];
+  }
+  const float me = am / n;  // mean - P
+  float m2 = 0.f;
+#pragma unroll
+  for (int s = 0; s < BN_SLICES; ++s) {
+    const float d = e[s] - me;
+    if (cnt[s] > 0.f) m2 += q[s] + cnt[s] * (d * d);
+  }
+  const float mu = P + me;
+  const float var = m2 / n;
   mean[c] = mu;
   rstd[c] = 1.f / sqrtf(var + eps);
   if (run_mean) {
@@ -316,13 +386,17 @@ __global__ void upsample2_bwd_kernel(const float* __restrict__ dy, float* __rest
 }
 
 // ---- evaluate(target_size): bilinear resize of the probabilities + composition at the crop's own resolution -------
-// torch's order: h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11), every product and sum rounded on its own
+// torch's order: h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11), every product and sum rounded on its own.
+// Plain operators under `fp contract(off)`: the __fmul_rn / __fadd_rn intrinsics are inline * and + that keep their own
+// `contract` flag, and the compiler fused them into a multiply-add in the unrolled grid-stride trip of
+// gate_comb_fwd_kernel; the pragma governs the operators written inside its block.
 __device__ __forceinline__ float bilinear_at(const float* __restrict__ p, int w, int y0, int y1, int x0, int x1, float wy,
                                              float wx) {
-  const float w0 = __fsub_rn(1.f, wx);
-  const float top = __fadd_rn(__fmul_rn(w0, p[y0 * w + x0]), __fmul_rn(wx, p[y0 * w + x1]));
-  const float bot = __fadd_rn(__fmul_rn(w0, p[y1 * w + x0]), __fmul_rn(wx, p[y1 * w + x1]));
-  return __fadd_rn(__fmul_rn(__fsub_rn(1.f, wy), top), __fmul_rn(wy, bot));
+#pragma clang fp contract(off)
+  const float w0 = 1.f - wx;
+  const float top = w0 * p[y0 * w + x0] + wx * p[y0 * w + x1];
+  const float bot = w0 * p[y1 * w + x0] + wx * p[y1 * w + x1];
+  return (1.f - wy) * top + wy * bot;
 }
 
 // object class:     dst f32 = bilinear(obj) > .5 ? cls : label
@@ -330,6 +404,7 @@ __device__ __forceinline__ float bilinear_at(const float* __restrict__ p, int w,
 __global__ void resize_compose_kernel(const float* __restrict__ comb, const float* __restrict__ obj, int C, int h, int w,
                                       const float* __restrict__ label, const float* __restrict__ mask, float cls,
                                       int background, void* __restrict__ dst, int H, int W, int align) {
+#pragma clang fp contract(off)
   const long long n = (long long)H * W;
   GS_LOOP(i, n) {
     const int ox = (int)(i % W), oy = (int)(i / W);
@@ -341,12 +416,12 @@ __global__ void resize_compose_kernel(const float* __restrict__ comb, const floa
     if (!background) {
       ((float*)dst)[i] = bilinear_at(obj, w, y0, y1, x0, x1, wy, wx) > 0.5f ? cls : l;
     } else {
-      const float m = mask[i], m1 = __fsub_rn(1.f, m);
+      const float m = mask[i], m1 = 1.f - m;
       long long best = 0;
       float bv = 0.f;
       for (int c = 0; c < C; ++c) {
         const float p = bilinear_at(comb + (long long)c * h * w, w, y0, y1, x0, x1, wy, wx);
-        const float v = __fadd_rn(__fmul_rn(p, m), __fmul_rn(m1, l == (float)c ? 1.f : 0.f));
+        const float v = p * m + m1 * (l == (float)c ? 1.f : 0.f);
         if (c == 0 || (bv == bv && (v > bv || v != v))) {
           bv = v;
           best = c;
@@ -390,12 +465,13 @@ __global__ void logsoftmax_bwd_kernel(const float* __restrict__ y, const float* 
 // The three products / the sum are rounded one by one (no fused multiply-add): the forward is torch's, bit for bit.
 __global__ void gate_comb_fwd_kernel(const float* __restrict__ ctx, const float* __restrict__ p, const float* __restrict__ obj,
                                      float* __restrict__ out, int B, int C, int hw) {
+#pragma clang fp contract(off)  // see bilinear_at: without it the unrolled trip fuses the second product into the sum
   const long long total = (long long)B * C * hw;
   GS_LOOP(i, total) {
     const int px = (int)(i % hw);
     const int b = (int)(i / ((long long)C * hw));
     const float g = p[(size_t)b * hw + px];
-    out[i] = __fadd_rn(__fmul_rn(__fsub_rn(1.f, g), ctx[i]), __fmul_rn(g, obj[(size_t)b * hw + px]));
+    out[i] = (1.f - g) * ctx[i] + g * obj[(size_t)b * hw + px];
   }
 }
 // dctx = (1 - p) * dout;  dobj = p * sum_c dout;  dp = sum_c dout * (obj - ctx)      (one thread per pixel walks the channels)
@@ -556,7 +632,8 @@ __global__ void lr_control_kernel(const float* __restrict__ d_real, const float*
 
 extern "C" {
 
-size_t him_batchnorm_ws(int C) { return ((size_t)C * BN_SLICES * 2 + (size_t)C * 2) * sizeof(float) + 256; }
+// forward: 3 floats per slice; backward: 2 per slice and the channel sums behind them
+size_t him_batchnorm_ws(int C) { return ((size_t)C * BN_SLICES * 3 + (size_t)C * 2) * sizeof(float) + 256; }
 
 int him_batchnorm_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* run_mean,
                       float* run_var, float* y, float* save_mean, float* save_rstd, int B, int C, int hw, float eps,
@@ -567,8 +644,8 @@ int him_batchnorm_fwd(const float* x, const float* residual, const float* gamma,
   if (!ws || ws_bytes < him_batchnorm_ws(C)) return fail(HIM_E_WORKSPACE, "batchnorm: ws too small");
   float* partial = (float*)ws;
   if (training) hipLaunchKernelGGL(bn_stats_kernel, dim3(C, BN_SLICES), dim3(256), 0, ST, x, partial, B, C, hw);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, ST, x, (const float*)partial, save_mean, save_rstd,
-                     run_mean, run_var, B, C, hw, BN_SLICES, eps, momentum, training);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, ST, (const float*)partial, save_mean, save_rstd,
+                     run_mean, run_var, B, C, hw, eps, momentum, training);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(cdiv(hw, 1024), B * C), dim3(256), 0, ST, x, residual, y, (const float*)save_mean,
                      (const float*)save_rstd, gamma, beta, C, hw, act, slope);
   return check_launch("batchnorm_fwd");
