@@ -705,8 +705,6 @@ static int run_wgrad(const HimAlgo& a, const float* dy, const float* x, float* d
 #undef HIM_WF
     int rc0 = check_launch("wgrad_fast");
     if (rc0) return rc0;
-    const long long n = (long long)M * p.Np;
-    (void)n;
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3(C / 64, M), dim3(256), 0, st, (const float*)ws, dw, M, C, KH * KW, fs,
                        accumulate);
     return check_launch("wgrad_finish");
@@ -756,6 +754,12 @@ static int run_bias_grad(const float* dy, float* db, int B, int C, int hw, int a
   hipLaunchKernelGGL(bias_grad1_kernel, dim3(C, nsl), dim3(256), 0, st, dy, (float*)ws, B, C, hw);
   hipLaunchKernelGGL(bias_grad2_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, (const float*)ws, db, C, nsl, accumulate);
   return check_launch("bias_grad");
+}
+// dbias of a weight-gradient call: its scratch sits behind the slab region (`off` bytes) of the call's workspace
+static int run_bias_grad_behind(const float* dy, float* db, int B, int C, int hw, int accumulate, void* ws, size_t ws_bytes,
+                                size_t off, hipStream_t st) {
+  if (ws_bytes < off) return fail(HIM_E_WORKSPACE, "bwd_weight ws too small");
+  return run_bias_grad(dy, db, B, C, hw, accumulate, (char*)ws + off, ws_bytes - off, st);
 }
 
 static int check_conv(const HimConv2d* d) {
@@ -812,9 +816,6 @@ static void fill_fprop(GConvP& g, const HimConv2d* d, const float* x, const floa
 }
 
 static const int SMALL_NSPLIT = 8;
-static bool small_split_ok(const HimConv2d* d) {
-  return d->Cout <= 4 && d->Cin >= 256 && (long long)d->B * d->OH * d->OW < 256 * 512;
-}
 // split-K factor of a single-phase fast launch: aim at >= 2 workgroups per CU when the output has few tiles
 static int fast_ksplit(const HimAlgo& a, int M, long long N, int nk) {
   if (algo_off(a, HIM_ALGO_NO_SPLITK)) return 1;
@@ -846,9 +847,6 @@ static int fast_ksplit(const HimAlgo& a, int M, long long N, int nk) {
   }
   return best;
 }
-static bool wino_fwd_ok(const HimConv2d* d) {
-  return wino_shape_ok(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad, d->H, d->W);
-}
 // The fused Winograd kernel (him_wino_fused.inc: transforms inside the GEMM kernel) takes the 3x3 stride-1 pad-1 layers
 // with 64..512 reduction channels and a multiple of 64 output channels in the FORWARD direction (zero or reflection
 // padding) and the data gradient of ZERO-padded layers: all VGG convs but conv1_1, the box2mask ResnetBlocks.
@@ -869,60 +867,93 @@ static bool wino_fused_ok(const HimAlgo& a, int Co, int Ci, int KH, int KW, int 
          wino_fused_shape_ok(Co, Ci, KH, KW, stride, pad, B, H, W);
 }
 // The persistent, wave-specialised form of the fused kernel (him_wino_fused2.inc) takes the launches of the fused range it
-// supports (even W, reduction channels % 8 == 0 and >= 32, NONE / RELU / LRELU epilogue); everything else -- and everything
-// under HIM_ALGO_NO_WINO_FUSED2 -- stays on him_wino_fused.inc.  Same weight panel: the choice is per launch, not per panel.
-static bool wino_fused2_ok(const HimAlgo& a, int Co, int Ci, int B, int H, int W, int act) {
-  return !algo_off(a, HIM_ALGO_NO_WINO_FUSED2) && algo_wino_fused_chunk(a) != 4 && wino_fused2_act_ok(act) &&
-         wino_fused2_shape_ok(Co, Ci, 3, 3, 1, 1, B, H, W);
+// supports (even W, reduction channels % 8 == 0 and >= 32, NONE / RELU / LRELU epilogue: wino_fused2_act_ok, asked per
+// launch); everything else -- and everything under HIM_ALGO_NO_WINO_FUSED2 -- stays on him_wino_fused.inc.  Same weight
+// panel: the choice is per launch, not per panel.
+static bool wino_fused2_ok(const HimAlgo& a, int Co, int Ci, int B, int H, int W) {
+  return !algo_off(a, HIM_ALGO_NO_WINO_FUSED2) && algo_wino_fused_chunk(a) != 4 && wino_fused2_shape_ok(Co, Ci, 3, 3, 1, 1, B, H, W);
 }
-static bool wino_fused_fwd_ok(const HimConv2d* d) {
-  return wino_fused_ok(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad, d->B, d->H, d->W);
+
+// ---- the dispatch plan --------------------------------------------------------------------------------------------------
+// Which kernel family runs the forward / the data gradient of a descriptor, with every sub-choice and the layout of its
+// workspace: a plain value, a pure function of the descriptor (no device query, no state).  plan_fprop / plan_dgrad are the
+// ONLY place the selection is written down: the runners, the size / panel / layout queries, the ResnetBlock, one-hot and
+// transposed-conv entry points all read it.  Families are tested in the order F(4x4), fused F(2x2), F(2x2), small-split,
+// fast GEMM, generic.
+enum ConvFamily {   // 0..4 are the codes him_conv2d_panel_layout answers
+  CONV_RAW = 0,          // generic / few-channel kernels on the raw weights (forward only)
+  CONV_GEMM = 1,         // implicit GEMM on a regrouped weight panel (`fast`: the MFMA kernel, 16-padded panel)
+  CONV_WINO = 2,         // Winograd F(2x2,3x3), separate transforms + batched GEMM
+  CONV_WINO_FUSED = 3,   // fused F(2x2,3x3) kernel (`fused2`: its persistent form where the activation allows)
+  CONV_WINO4 = 4,        // Winograd F(4x4,3x3), frozen weights
+  CONV_SMALL_SPLIT = 5,  // the tiny-M head kernel on the raw weights with the channels split over `ksplit` slabs
+};
+struct ConvPlan {
+  ConvFamily family;
+  bool fast, fused2;
+  bool dfold;          // dgrad GEMM: reflect-pad-1 3x3 gathered from the border-extended gradient at dpad_off
+  bool refl_pad;       // dgrad: reflect padding through the padded gradient at dpad_off + reflect_fold_kernel
+  bool wino_fold;      // dgrad F(2x2): reflect folded into the border tiles' patches (see wino_input_kernel)
+  bool wino_epilogue;  // dgrad: an F(2x2) descriptor on the GEMM path because of a fused bias / activation
+  bool in_act_slab;    // forward: him_conv2d_in_act_fwd hands the split-K slabs to the InstanceNorm kernel
+  int ksplit;          // split-K slabs at kpart_off (1: none)
+  size_t panel_floats;  // the regrouped weights the queries report, at the start of the workspace unless prebuilt (0: raw)
+  size_t keep_floats;   // forward F(2x2): the transformed input the weight gradient can reuse (0: not kept)
+  size_t pad_floats;    // dgrad: floats of the padded gradient = one split-K slab of the reflect detour
+  size_t scratch_off, dpad_off, kpart_off;  // float offsets: transform scratch, extended / padded gradient, split-K slabs
+  size_t ws_bytes;
+};
+static size_t round64(size_t n) { return (n + 63) / 64 * 64; }
+
+static ConvPlan plan_fprop(const HimConv2d* d) {
+  const HimAlgo& a = d->algo;
+  const int Co = d->Cout, Ci = d->Cin, KK = d->KH * d->KW;
+  const size_t outn = (size_t)d->B * Co * d->OH * d->OW;
+  ConvPlan p;
+  memset(&p, 0, sizeof(p));
+  p.ksplit = 1;
+  if (wino4_shape_ok(a, Co, Ci, d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->B, d->H, d->W) ||
+      wino4_shape_ok(a, Co, Ci, d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->B, d->H, d->W, true)) {
+    p.family = CONV_WINO4;   // frozen-weight layers (him_conv_wino4.inc)
+    p.panel_floats = p.scratch_off = wino4_panel_floats(Co, Ci);
+    p.ws_bytes = (p.scratch_off + wino4_ws_floats(d->B, Co, Ci, d->H, d->W)) * sizeof(float) + 256;
+  } else if (wino_fused_ok(a, Co, Ci, d->KH, d->KW, d->stride, d->pad, d->B, d->H, d->W)) {
+    p.family = CONV_WINO_FUSED;
+    p.fused2 = wino_fused2_ok(a, Co, Ci, d->B, d->H, d->W);
+    p.panel_floats = wino_fused_panel_floats(Co, Ci);
+    p.ws_bytes = p.panel_floats * sizeof(float) + 256;
+  } else if (wino_shape_ok(a, Co, Ci, d->KH, d->KW, d->stride, d->pad, d->H, d->W)) {
+    p.family = CONV_WINO;
+    p.panel_floats = p.scratch_off = (size_t)16 * Co * Ci;
+    p.ws_bytes = (p.scratch_off + wino_conv_floats(d->B, Ci, Co, d->OH, d->OW)) * sizeof(float) + 256;
+    // kept input transform: where the weight gradient runs F(2x2) on the LDS-DMA GEMM (wino_wgrad_ok, run_wgrad's kept_v)
+    const WinoGeom g = wino_geom(d->B, Ci, d->H, d->W, d->OH, d->OW, 1);
+    if ((Co % 128) == 0 && (Ci % 128) == 0 && d->OH == d->H && d->OW == d->W && !algo_off(a, HIM_ALGO_NO_BGEMM) &&
+        bgemm_shape_ok(Co, g.Tp, Ci, 16))
+      p.keep_floats = (size_t)16 * Ci * g.Tp;
+  } else if (Co <= 4 && Ci >= 256 && (long long)d->B * d->OH * d->OW < 256 * 512) {
+    p.family = CONV_SMALL_SPLIT;   // too few positions to fill the chip: launch_small_cfg splits the channels
+    p.ksplit = SMALL_NSPLIT;
+    p.ws_bytes = (size_t)SMALL_NSPLIT * outn * sizeof(float) + 256;
+  } else if (use_fast(a, Co, Ci)) {
+    p.family = CONV_GEMM;
+    p.fast = true;
+    p.panel_floats = (size_t)Co * KK * pad16(Ci);
+    p.ksplit = fast_ksplit(a, Co, (long long)d->B * d->OH * d->OW, KK * (pad16(Ci) / 16));
+    p.kpart_off = round64(p.panel_floats);
+    p.ws_bytes = (p.kpart_off + (p.ksplit > 1 ? p.ksplit * outn : 0)) * sizeof(float) + 256;
+    // Conv2d -> InstanceNorm in one call: the few-tile layers (PatchGAN blocks, the last generator down-convolutions) whose
+    // forward is ONE split-K launch (not batch-sliced at 2 GiB) leave their slabs to the norm.  launch_gconv's earlier
+    // exits (tiny-M kernel, few-channel tiled kernel) never see such a descriptor: use_fast asks for Cout > 4, Cin >= 16.
+    p.in_act_slab = p.ksplit > 1 && d->act == HIM_ACT_NONE && (unsigned long long)d->B * Ci * d->H * d->W * 4ull < (1ull << 31);
+  }
+  // The one place the queries and the execution part: the Winograd tests do not all ask for use_fast (GENERIC_CONV, or a
+  // channel threshold lowered below 16 / to Cout <= 4), and such a descriptor still RUNS its Winograd family with the
+  // workspace above -- but reports no panel and layout 0, so no panel is ever built or accepted for it.
+  if (!use_fast(a, Co, Ci)) p.panel_floats = 0;
+  return p;
 }
-// data gradient of a ZERO-padded 3x3 stride-1 conv = the same convolution with the flipped / transposed filter
-static bool wino_fused_dgrad_ok(const HimConv2d* d) {
-  return d->pad_mode == HIM_PAD_ZERO && d->OH == d->H && d->OW == d->W &&
-         wino_fused_ok(d->algo, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad, d->B, d->H, d->W);
-}
-// F(4x4,3x3) for frozen-weight layers (him_conv_wino4.inc); checked BEFORE the F(2x2,3x3) forms
-static bool wino4_fwd_ok(const HimConv2d* d) {
-  return wino4_shape_ok(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->B, d->H, d->W) ||
-         wino4_shape_ok(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->B, d->H, d->W, true);
-}
-static bool wino4_dgrad_ok(const HimConv2d* d) {
-  return d->OH == d->H && d->OW == d->W &&
-         wino4_shape_ok(d->algo, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->B, d->H, d->W);
-}
-static size_t fprop_ws_bytes(const HimConv2d* d) {
-  if (wino4_fwd_ok(d))
-    return (wino4_panel_floats(d->Cout, d->Cin) + wino4_ws_floats(d->B, d->Cout, d->Cin, d->H, d->W)) * sizeof(float) + 256;
-  if (wino_fused_fwd_ok(d)) return wino_fused_panel_floats(d->Cout, d->Cin) * sizeof(float) + 256;
-  if (wino_fwd_ok(d))
-    return ((size_t)16 * d->Cout * d->Cin + wino_conv_floats(d->B, d->Cin, d->Cout, d->OH, d->OW)) * sizeof(float) + 256;
-  if (small_split_ok(d)) return (size_t)SMALL_NSPLIT * d->Cout * d->B * d->OH * d->OW * sizeof(float) + 256;
-  if (!use_fast(d->algo, d->Cout, d->Cin)) return 0;
-  const int ks = fast_ksplit(d->algo, d->Cout, (long long)d->B * d->OH * d->OW, d->KH * d->KW * (pad16(d->Cin) / 16));
-  const size_t wts = ((size_t)d->Cout * d->KH * d->KW * pad16(d->Cin) * sizeof(float) + 255) / 256 * 256;
-  return wts + (ks > 1 ? (size_t)ks * d->B * d->Cout * d->OH * d->OW * sizeof(float) : 0) + 256;
-}
-// floats of the regrouped weight panel the forward kernel reads (0: it reads the raw weights)
-static size_t fprop_panel_floats(const HimConv2d* d) {
-  if (small_split_ok(d) || d->Cout <= 4 || !use_fast(d->algo, d->Cout, d->Cin)) return 0;
-  if (wino4_fwd_ok(d)) return wino4_panel_floats(d->Cout, d->Cin);
-  if (wino_fused_fwd_ok(d)) return wino_fused_panel_floats(d->Cout, d->Cin);
-  if (wino_fwd_ok(d)) return (size_t)16 * d->Cout * d->Cin;
-  return (size_t)d->Cout * d->KH * d->KW * pad16(d->Cin);
-}
-// Conv2d -> InstanceNorm in one call (him_conv2d_in_act_fwd): the descriptors whose forward is a split-K launch of the fast
-// implicit-GEMM kernel -- the few-tile layers (PatchGAN blocks, the last generator down-convolutions) -- hand their slabs to
-// the InstanceNorm kernel.  Same conditions, in the same order, as run_fprop's dispatch.
-static bool in_act_slab_ok(const HimConv2d* d) {
-  if (wino4_fwd_ok(d) || wino_fused_fwd_ok(d) || wino_fwd_ok(d) || small_split_ok(d)) return false;
-  if (!use_fast(d->algo, d->Cout, d->Cin) || d->act != HIM_ACT_NONE) return false;
-  if ((unsigned long long)d->B * d->Cin * d->H * d->W * 4ull >= (1ull << 31)) return false;   // batch-sliced launches
-  // launch_gconv's earlier exits (tiny-M kernel, few-channel tiled kernel) never see a fast split-K descriptor: Cout > 4
-  // and Cin >= 16 are what use_fast asks for
-  return fast_ksplit(d->algo, d->Cout, (long long)d->B * d->OH * d->OW, d->KH * d->KW * (pad16(d->Cin) / 16)) > 1;
-}
+
 // panel == nullptr: regroup the weights into the workspace on every call; build_only: write the panel to ws and return
 // defer (him_conv2d_in_act_fwd): a split-K launch leaves its raw slabs in the workspace and reports them instead of
 // running the finish pass (bias / activation / y are then the caller's: the InstanceNorm kernel reads the slabs)
@@ -933,97 +964,88 @@ struct FpropDefer {
 static int run_fprop(const HimConv2d* d, const float* x, const float* w, const float* bias, float* y, void* ws,
                      size_t ws_bytes, hipStream_t st, const float* panel = nullptr, bool build_only = false,
                      float* keep = nullptr, FpropDefer* defer = nullptr) {
-  if (wino4_fwd_ok(d)) {
-    const size_t pf = wino4_panel_floats(d->Cout, d->Cin);
-    const size_t need = build_only ? pf * sizeof(float) : fprop_ws_bytes(d);
-    if (!ws || ws_bytes < need) return fail(HIM_E_WORKSPACE, "conv fwd needs %zu ws bytes, got %zu", need, ws_bytes);
-    float* U = (float*)ws;
-    if (!panel) {
-      hipLaunchKernelGGL((wino4_weight_kernel<0>), dim3(cdiv(d->Cin, 256), d->Cout), dim3(256), 0, st, w, U, d->Cout, d->Cin);
-      int rc = check_launch("wino4_weight");
-      if (rc || build_only) return rc;
-    }
-    return run_wino4_conv(d->B, d->Cin, d->H, d->W, d->Cout, x, panel ? panel : U, bias, d->act, d->slope, y, U + pf, st,
-                          nullptr, d->pad_mode == HIM_PAD_REFLECT, !algo_off(d->algo, HIM_ALGO_NO_BGEMM_PERSISTENT));
-  }
-  if (wino_fused_fwd_ok(d)) {
-    if (!panel) {
-      // the size him_conv2d_fwd_ws answers, as on every other path (a workspace one byte short of it is refused)
-      const size_t need = build_only ? wino_fused_panel_floats(d->Cout, d->Cin) * sizeof(float) : fprop_ws_bytes(d);
-      if (!ws || ws_bytes < need) return fail(HIM_E_WORKSPACE, "conv fwd needs %zu ws bytes, got %zu", need, ws_bytes);
-      hipLaunchKernelGGL((wino_fused_weight_kernel<0>), dim3(cdiv(d->Cin, 256), d->Cout), dim3(256), 0, st, w, (float*)ws,
-                         d->Cout, d->Cin);
-      int rc = check_launch("wino_fused_weight");
-      if (rc || build_only) return rc;
-    }
-    if (wino_fused2_ok(d->algo, d->Cout, d->Cin, d->B, d->H, d->W, d->act))     // persistent form (round 6), same panel
-      return run_wino_fused2(d->B, d->Cin, d->H, d->W, d->Cout, d->pad_mode == HIM_PAD_REFLECT, x,
-                             panel ? panel : (const float*)ws, bias, d->act, d->slope, y, st, nullptr, device_cus());
-    return run_wino_fused(d->B, d->Cin, d->H, d->W, d->Cout, d->pad_mode == HIM_PAD_REFLECT, x,
-                          panel ? panel : (const float*)ws, bias, d->act, d->slope, y, st, nullptr,
-                          algo_wino_fused_chunk(d->algo) == 4);
-  }
-  if (wino_fwd_ok(d)) {
-    const size_t need = build_only ? fprop_panel_floats(d) * sizeof(float) : fprop_ws_bytes(d);
-    if (!ws || ws_bytes < need) return fail(HIM_E_WORKSPACE, "conv fwd needs %zu ws bytes, got %zu", need, ws_bytes);
-    float* U = (float*)ws;
-    if (!panel) {
-      hipLaunchKernelGGL((wino_weight_kernel<0>), dim3(cdiv(d->Cin, wino_tblock(d->algo)), d->Cout), dim3(wino_tblock(d->algo)), 0, st, w, U, d->Cout,
-                         d->Cin);
-      int rc = check_launch("wino_weight");
-      if (rc || build_only) return rc;
-    }
-    return run_wino_conv(d->algo, d->B, d->Cin, d->H, d->W, d->Cout, d->OH, d->OW, 1, d->pad_mode == HIM_PAD_REFLECT, x,
-                         panel ? panel : U, bias, d->act, d->slope, y, U + (size_t)16 * d->Cout * d->Cin, st, false, false,
-                         keep);
+  const ConvPlan p = plan_fprop(d);
+  // the size him_conv2d_fwd_ws answers on every path (a workspace one byte short of it is refused), prebuilt panel or
+  // not -- except the fused kernel, which with its panel needs no workspace at all
+  const size_t need = build_only ? p.panel_floats * sizeof(float) : p.ws_bytes;
+  if (need && !(p.family == CONV_WINO_FUSED && panel) && (!ws || ws_bytes < need))
+    return fail(HIM_E_WORKSPACE, "conv fwd needs %zu ws bytes, got %zu", need, ws_bytes);
+  float* const wsf = (float*)ws;
+  const float* const U = panel ? panel : wsf;
+  const bool reflect = d->pad_mode == HIM_PAD_REFLECT;
+  switch (p.family) {
+    case CONV_WINO4:
+      if (!panel) {
+        hipLaunchKernelGGL((wino4_weight_kernel<0>), dim3(cdiv(d->Cin, 256), d->Cout), dim3(256), 0, st, w, wsf, d->Cout, d->Cin);
+        int rc = check_launch("wino4_weight");
+        if (rc || build_only) return rc;
+      }
+      return run_wino4_conv(d->B, d->Cin, d->H, d->W, d->Cout, x, U, bias, d->act, d->slope, y, wsf + p.scratch_off, st,
+                            nullptr, reflect, !algo_off(d->algo, HIM_ALGO_NO_BGEMM_PERSISTENT));
+    case CONV_WINO_FUSED:
+      if (!panel) {
+        hipLaunchKernelGGL((wino_fused_weight_kernel<0>), dim3(cdiv(d->Cin, 256), d->Cout), dim3(256), 0, st, w, wsf,
+                           d->Cout, d->Cin);
+        int rc = check_launch("wino_fused_weight");
+        if (rc || build_only) return rc;
+      }
+      if (p.fused2 && wino_fused2_act_ok(d->act))     // persistent form (round 6), same panel
+        return run_wino_fused2(d->B, d->Cin, d->H, d->W, d->Cout, reflect, x, U, bias, d->act, d->slope, y, st, nullptr,
+                               device_cus());
+      return run_wino_fused(d->B, d->Cin, d->H, d->W, d->Cout, reflect, x, U, bias, d->act, d->slope, y, st, nullptr,
+                            algo_wino_fused_chunk(d->algo) == 4);
+    case CONV_WINO:
+      if (!panel) {
+        hipLaunchKernelGGL((wino_weight_kernel<0>), dim3(cdiv(d->Cin, wino_tblock(d->algo)), d->Cout), dim3(wino_tblock(d->algo)), 0, st, w, wsf, d->Cout,
+                           d->Cin);
+        int rc = check_launch("wino_weight");
+        if (rc || build_only) return rc;
+      }
+      return run_wino_conv(d->algo, d->B, d->Cin, d->H, d->W, d->Cout, d->OH, d->OW, 1, reflect, x, U, bias, d->act, d->slope,
+                           y, wsf + p.scratch_off, st, false, false, keep);
+    default: break;
   }
   GConvP g;
   fill_fprop(g, d, x, w, bias, y);
-  if (small_split_ok(d)) {
-    if (!ws || ws_bytes < fprop_ws_bytes(d)) return fail(HIM_E_WORKSPACE, "conv fwd ws too small");
-    g.small_part = (float*)ws;
-    g.small_nsplit = SMALL_NSPLIT;
-  }
-  if (use_fast(d->algo, d->Cout, d->Cin)) {
-    const size_t need = build_only ? fprop_panel_floats(d) * sizeof(float) : fprop_ws_bytes(d);
-    if (!ws || ws_bytes < need) return fail(HIM_E_WORKSPACE, "conv fwd needs %zu ws bytes, got %zu", need, ws_bytes);
-    WT2P t;
-    memset(&t, 0, sizeof(t));
-    const int KK = d->KH * d->KW;
-    t.W = w;
-    t.M = d->Cout;
-    t.C2 = d->Cin;
-    t.C2p = pad16(d->Cin);
-    t.sm = (long long)d->Cin * KK;
-    t.sc = KK;
-    t.ph[0].out = (float*)ws;
-    t.ph[0].JH = d->KH;
-    t.ph[0].JW = d->KW;
-    t.ph[0].sh = d->KW;
-    t.ph[0].sw = 1;
-    t.ph[0].base = 0;
-    t.ph[0].total = (long long)d->Cout * KK * t.C2p;
+  if (p.family == CONV_SMALL_SPLIT) {
+    g.small_part = wsf + p.kpart_off;
+    g.small_nsplit = p.ksplit;
+  } else if (p.family == CONV_GEMM) {
+    const int KK = d->KH * d->KW, C2p = pad16(d->Cin);
     if (!panel) {
-      if (KK <= 64)
-        hipLaunchKernelGGL(wt_fwd_kernel, dim3(t.C2p / 16, d->Cout), dim3(64), 0, st, w, (float*)ws, d->Cout, d->Cin,
-                           t.C2p / 16, KK);
-      else
+      if (KK <= 64) {
+        hipLaunchKernelGGL(wt_fwd_kernel, dim3(C2p / 16, d->Cout), dim3(64), 0, st, w, wsf, d->Cout, d->Cin, C2p / 16, KK);
+      } else {
+        WT2P t;
+        memset(&t, 0, sizeof(t));
+        t.W = w;
+        t.M = d->Cout;
+        t.C2 = d->Cin;
+        t.C2p = C2p;
+        t.sm = (long long)d->Cin * KK;
+        t.sc = KK;
+        t.ph[0].out = wsf;
+        t.ph[0].JH = d->KH;
+        t.ph[0].JW = d->KW;
+        t.ph[0].sh = d->KW;
+        t.ph[0].sw = 1;
+        t.ph[0].base = 0;
+        t.ph[0].total = (long long)p.panel_floats;
         hipLaunchKernelGGL(wtrans2_kernel, dim3(std::min<long long>(cdiv(t.ph[0].total, 256), 4096), 1), dim3(256), 0, st, t);
+      }
       int rc = check_launch("wtrans2");
       if (rc || build_only) return rc;
     }
     g.fast = 1;
-    g.ph[0].At = panel ? panel : (const float*)ws;
-    g.ph[0].C2p = t.C2p;
-    const int ks = fast_ksplit(d->algo, d->Cout, (long long)d->B * d->OH * d->OW, KK * (t.C2p / 16));
-    if (ks > 1) {
-      const size_t wts = ((size_t)d->Cout * KK * t.C2p * sizeof(float) + 255) / 256 * 256;
-      g.ksplit = ks;
-      g.kpart = (float*)((char*)ws + wts);
-      if (defer && in_act_slab_ok(d)) {
+    g.ph[0].At = U;
+    g.ph[0].C2p = C2p;
+    if (p.ksplit > 1) {
+      g.ksplit = p.ksplit;
+      g.kpart = wsf + p.kpart_off;
+      if (defer && p.in_act_slab) {
         g.kno_finish = 1;
         defer->slabs = g.kpart;
-        defer->ks = ks;
+        defer->ks = p.ksplit;
       }
     }
   }
@@ -1032,115 +1054,128 @@ static int run_fprop(const HimConv2d* d, const float* x, const float* w, const f
 
 // data gradient of the conv described by `d` (also the forward of its transposed conv):
 // out (B,Cin,H,W) = sum W * g (B,Cout,OH,OW); for reflect mode goes through the padded gradient + fold.
-// reflect-pad-1 3x3 stride-1 (every ResnetBlock conv): gather from the border-extended gradient, no padded GEMM columns
-static bool dfold_ok(const HimConv2d* d) {
-  return !algo_off(d->algo, HIM_ALGO_NO_DFOLD) && d->pad_mode == HIM_PAD_REFLECT && d->pad == 1 && d->KH == 3 && d->KW == 3 && d->stride == 1 &&
-         d->H >= 3 && d->W >= 3 && d->OH == d->H && d->OW == d->W && use_fast(d->algo, d->Cin, d->Cout);
+// epilogue: the call fuses a bias / activation (the transposed conv's forward).  The separate-transform F(2x2) pipeline
+// has no such epilogue: the call takes the GEMM path -- inside the workspace the QUERIES (epilogue = false) sized, and
+// with a prebuilt panel, which is then the Winograd one, it is refused.
+static ConvPlan plan_dgrad(const HimConv2d* d, bool epilogue) {
+  const HimAlgo& a = d->algo;
+  const int Co = d->Cout, Ci = d->Cin, KK = d->KH * d->KW;
+  const bool same = d->OH == d->H && d->OW == d->W, reflect = d->pad_mode == HIM_PAD_REFLECT;
+  ConvPlan p;
+  memset(&p, 0, sizeof(p));
+  p.ksplit = 1;
+  if (same && wino4_shape_ok(a, Ci, Co, d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->B, d->H, d->W)) {
+    p.family = CONV_WINO4;   // frozen weights, zero padding: the convolution of gy with the rotated / transposed filter
+    p.panel_floats = p.scratch_off = wino4_panel_floats(Ci, Co);
+    p.ws_bytes = (p.scratch_off + wino4_ws_floats(d->B, Ci, Co, d->H, d->W)) * sizeof(float) + 256;
+    return p;
+  }
+  if (d->pad_mode == HIM_PAD_ZERO && same && wino_fused_ok(a, Ci, Co, d->KH, d->KW, d->stride, d->pad, d->B, d->H, d->W)) {
+    p.family = CONV_WINO_FUSED;   // zero-padded 3x3 stride-1: the same convolution with the flipped / transposed filter
+    p.fused2 = wino_fused2_ok(a, Ci, Co, d->B, d->OH, d->OW);
+    p.panel_floats = wino_fused_panel_floats(Ci, Co);
+    p.ws_bytes = p.panel_floats * sizeof(float) + 256;
+    return p;
+  }
+  const bool wino = same && wino_shape_ok(a, Ci, Co, d->KH, d->KW, d->stride, d->pad, d->H, d->W);
+  if (wino && !epilogue) {
+    p.family = CONV_WINO;   // the FORWARD panel, read transposed (U' + V + Mo, + the padded gradient for unfolded reflect)
+    p.wino_fold = reflect && (d->H % 2) == 0 && (d->W % 2) == 0 && d->H >= 4 && d->W >= 4 && !algo_off(a, HIM_ALGO_WINO_PADDED_DGRAD);
+    p.refl_pad = reflect && !p.wino_fold;
+    const int GH = p.refl_pad ? d->H + 2 : d->H, GW = p.refl_pad ? d->W + 2 : d->W;
+    p.panel_floats = p.scratch_off = (size_t)16 * Ci * Co;
+    p.dpad_off = p.scratch_off + wino_conv_floats(d->B, Co, Ci, GH, GW);
+    p.pad_floats = p.refl_pad ? (size_t)d->B * Ci * GH * GW : 0;
+    p.ws_bytes = (p.dpad_off + p.pad_floats) * sizeof(float) + 256;
+    return p;
+  }
+  p.family = CONV_GEMM;
+  p.wino_epilogue = wino;
+  p.fast = use_fast(a, Ci, Co);
+  // reflect-pad-1 3x3 stride-1 (every ResnetBlock conv): gather from the border-extended gradient, no padded GEMM columns
+  p.dfold = !algo_off(a, HIM_ALGO_NO_DFOLD) && reflect && d->pad == 1 && d->KH == 3 && d->KW == 3 && d->stride == 1 &&
+            d->H >= 3 && d->W >= 3 && same && p.fast;
+  p.refl_pad = reflect && !p.dfold;
+  p.panel_floats = (size_t)Ci * (p.fast ? pad16(Co) : Co) * KK;
+  const long long PH = d->H + 2 * d->pad, PW = d->W + 2 * d->pad;
+  p.pad_floats = (size_t)d->B * Ci * PH * PW;
+  if (d->stride == 1 && p.fast)   // one phase
+    p.ksplit = fast_ksplit(a, Ci, (long long)d->B * (p.refl_pad ? PH * PW : d->H * d->W), KK * (pad16(Co) / 16));
+  const size_t extn = p.dfold ? (size_t)d->B * Co * (d->OH + 2) * (d->OW + 2) : 0;
+  p.dpad_off = round64(p.panel_floats);
+  p.kpart_off = p.dpad_off + round64(p.refl_pad ? p.pad_floats : extn);
+  // the size is an upper bound of that layout: the panel counted 16-padded, 64 floats of slack per region
+  size_t n = (size_t)Ci * pad16(Co) * KK + 64;
+  if (p.dfold) n += extn + 64;
+  else if (reflect) n += p.pad_floats + 64;
+  if (p.ksplit > 1) n += p.ksplit * p.pad_floats + 64;
+  p.ws_bytes = wino ? plan_dgrad(d, false).ws_bytes : n * sizeof(float) + 256;
+  return p;
 }
-static bool wino_dgrad_ok(const HimConv2d* d) {
-  return wino_shape_ok(d->algo, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad, d->H, d->W) && d->OH == d->H && d->OW == d->W;
-}
-static bool wino_dgrad_fold(const HimConv2d* d) {  // reflect folded into the border tiles' patches (see wino_input_kernel)
-  return d->pad_mode == HIM_PAD_REFLECT && (d->H % 2) == 0 && (d->W % 2) == 0 && d->H >= 4 && d->W >= 4 &&
-         !algo_off(d->algo, HIM_ALGO_WINO_PADDED_DGRAD);
-}
-static size_t wino_dgrad_floats(const HimConv2d* d) {  // U' + V + Mo (+ padded gradient for reflect)
-  const bool refl = d->pad_mode == HIM_PAD_REFLECT && !wino_dgrad_fold(d);
-  const int GH = refl ? d->H + 2 : d->H, GW = refl ? d->W + 2 : d->W;
-  return (size_t)16 * d->Cin * d->Cout + wino_conv_floats(d->B, d->Cout, d->Cin, GH, GW) +
-         (refl ? (size_t)d->B * d->Cin * GH * GW : 0);
-}
-static int dgrad_ksplit(const HimConv2d* d) {
-  if (d->stride != 1 || !use_fast(d->algo, d->Cin, d->Cout)) return 1;
-  const bool refl = d->pad_mode == HIM_PAD_REFLECT && !dfold_ok(d);
-  const long long N = (long long)d->B * (refl ? d->H + 2 * d->pad : d->H) * (refl ? d->W + 2 * d->pad : d->W);
-  return fast_ksplit(d->algo, d->Cin, N, d->KH * d->KW * (pad16(d->Cout) / 16));
-}
-static size_t dgrad_ws_bytes(const HimConv2d* d) {
-  if (wino4_dgrad_ok(d))
-    return (wino4_panel_floats(d->Cin, d->Cout) + wino4_ws_floats(d->B, d->Cin, d->Cout, d->H, d->W)) * sizeof(float) + 256;
-  if (wino_fused_dgrad_ok(d)) return wino_fused_panel_floats(d->Cin, d->Cout) * sizeof(float) + 256;
-  if (wino_dgrad_ok(d)) return wino_dgrad_floats(d) * sizeof(float) + 256;
-  size_t n = (size_t)d->Cin * pad16(d->Cout) * d->KH * d->KW + 64;
-  const size_t outn = (size_t)d->B * d->Cin * (d->H + 2 * d->pad) * (d->W + 2 * d->pad);
-  if (dfold_ok(d)) n += (size_t)d->B * d->Cout * (d->OH + 2) * (d->OW + 2) + 64;
-  else if (d->pad_mode == HIM_PAD_REFLECT) n += outn + 64;
-  const int ks = dgrad_ksplit(d);
-  if (ks > 1) n += (size_t)ks * outn + 64;
-  return n * sizeof(float) + 256;
-}
-static size_t dgrad_panel_floats(const HimConv2d* d) {
-  if (wino4_dgrad_ok(d)) return wino4_panel_floats(d->Cin, d->Cout);
-  if (wino_fused_dgrad_ok(d)) return wino_fused_panel_floats(d->Cin, d->Cout);
-  if (wino_dgrad_ok(d)) return (size_t)16 * d->Cin * d->Cout;
-  return (size_t)d->Cin * (use_fast(d->algo, d->Cin, d->Cout) ? pad16(d->Cout) : d->Cout) * d->KH * d->KW;
-}
+
 // panel == nullptr: regroup the weights into the workspace on every call; build_only: write the panel to ws and return
 static int run_dgrad(const HimConv2d* d, const float* gy, const float* w, float* out, const float* bias, int act,
                      float slope, void* ws, size_t ws_bytes, hipStream_t st, const float* panel = nullptr,
                      bool build_only = false, const float* relu_mask = nullptr, bool* mask_done = nullptr) {
-  const size_t need = build_only ? dgrad_panel_floats(d) * sizeof(float) : dgrad_ws_bytes(d);
+  const ConvPlan p = plan_dgrad(d, bias || act != HIM_ACT_NONE);
+  const size_t need = build_only ? p.panel_floats * sizeof(float) : p.ws_bytes;
   if (!ws || ws_bytes < need) return fail(HIM_E_WORKSPACE, "dgrad needs %zu ws bytes, got %zu", need, ws_bytes);
-  if (wino4_dgrad_ok(d)) {   // frozen weights, zero padding: the convolution of gy with the rotated / transposed filter
-    const size_t pf = wino4_panel_floats(d->Cin, d->Cout);
-    float* U = (float*)ws;
-    if (!panel) {
-      hipLaunchKernelGGL((wino4_weight_kernel<1>), dim3(cdiv(d->Cout, 256), d->Cin), dim3(256), 0, st, w, U, d->Cin, d->Cout);
-      int rcu = check_launch("wino4_weight");
-      if (rcu || build_only) return rcu;
-    }
-    if (mask_done) *mask_done = relu_mask != nullptr;   // the gate rides in the output transform
-    return run_wino4_conv(d->B, d->Cout, d->OH, d->OW, d->Cin, gy, panel ? panel : U, bias, act, slope, out, U + pf, st,
-                          relu_mask, false, !algo_off(d->algo, HIM_ALGO_NO_BGEMM_PERSISTENT));
-  }
-  if (wino_fused_dgrad_ok(d)) {   // zero-padded 3x3 stride-1: the convolution of gy with the flipped / transposed filter
-    if (!panel) {
-      hipLaunchKernelGGL((wino_fused_weight_kernel<1>), dim3(cdiv(d->Cout, 256), d->Cin), dim3(256), 0, st, w, (float*)ws,
-                         d->Cin, d->Cout);
-      int rcu = check_launch("wino_fused_weight");
-      if (rcu || build_only) return rcu;
-    }
-    if (mask_done) *mask_done = relu_mask != nullptr;   // the gate rides in this kernel's epilogue
-    if (wino_fused2_ok(d->algo, d->Cin, d->Cout, d->B, d->OH, d->OW, act))
-      return run_wino_fused2(d->B, d->Cout, d->OH, d->OW, d->Cin, false, gy, panel ? panel : (const float*)ws, bias, act,
-                             slope, out, st, relu_mask, device_cus());
-    return run_wino_fused(d->B, d->Cout, d->OH, d->OW, d->Cin, false, gy, panel ? panel : (const float*)ws, bias, act, slope,
-                          out, st, relu_mask, algo_wino_fused_chunk(d->algo) == 4);
-  }
-  if (wino_dgrad_ok(d) && panel && (bias || act != HIM_ACT_NONE))
+  if (p.wino_epilogue && panel)
     return fail(HIM_E_UNSUPPORTED, "dgrad: Winograd panel with a fused bias/activation epilogue");
-  if (wino_dgrad_ok(d) && (build_only || (!bias && act == HIM_ACT_NONE))) {
-    float* U = (float*)ws;
-    if (!panel) {   // the FORWARD panel: the batched GEMM below reads it transposed (no flipped panel, round 3)
-      hipLaunchKernelGGL((wino_weight_kernel<0>), dim3(cdiv(d->Cin, wino_tblock(d->algo)), d->Cout), dim3(wino_tblock(d->algo)), 0, st, w, U, d->Cout,
-                         d->Cin);
-      int rcu = check_launch("wino_weight");
-      if (rcu || build_only) return rcu;
+  float* const wsf = (float*)ws;
+  const float* const U = panel ? panel : wsf;
+  switch (p.family) {
+    case CONV_WINO4:
+      if (!panel) {
+        hipLaunchKernelGGL((wino4_weight_kernel<1>), dim3(cdiv(d->Cout, 256), d->Cin), dim3(256), 0, st, w, wsf, d->Cin, d->Cout);
+        int rcu = check_launch("wino4_weight");
+        if (rcu || build_only) return rcu;
+      }
+      if (mask_done) *mask_done = relu_mask != nullptr;   // the gate rides in the output transform
+      return run_wino4_conv(d->B, d->Cout, d->OH, d->OW, d->Cin, gy, U, bias, act, slope, out, wsf + p.scratch_off, st,
+                            relu_mask, false, !algo_off(d->algo, HIM_ALGO_NO_BGEMM_PERSISTENT));
+    case CONV_WINO_FUSED:
+      if (!panel) {
+        hipLaunchKernelGGL((wino_fused_weight_kernel<1>), dim3(cdiv(d->Cout, 256), d->Cin), dim3(256), 0, st, w, wsf,
+                           d->Cin, d->Cout);
+        int rcu = check_launch("wino_fused_weight");
+        if (rcu || build_only) return rcu;
+      }
+      if (mask_done) *mask_done = relu_mask != nullptr;   // the gate rides in this kernel's epilogue
+      if (p.fused2 && wino_fused2_act_ok(act))
+        return run_wino_fused2(d->B, d->Cout, d->OH, d->OW, d->Cin, false, gy, U, bias, act, slope, out, st, relu_mask,
+                               device_cus());
+      return run_wino_fused(d->B, d->Cout, d->OH, d->OW, d->Cin, false, gy, U, bias, act, slope, out, st, relu_mask,
+                            algo_wino_fused_chunk(d->algo) == 4);
+    case CONV_WINO: {
+      if (!panel) {   // the FORWARD panel: the batched GEMM below reads it transposed (no flipped panel, round 3)
+        hipLaunchKernelGGL((wino_weight_kernel<0>), dim3(cdiv(d->Cin, wino_tblock(d->algo)), d->Cout), dim3(wino_tblock(d->algo)), 0, st, w, wsf, d->Cout,
+                           d->Cin);
+        int rcu = check_launch("wino_weight");
+        if (rcu || build_only) return rcu;
+      }
+      const bool rf = p.refl_pad;
+      const int GH = rf ? d->H + 2 : d->H, GW = rf ? d->W + 2 : d->W;
+      float* dpadw = wsf + p.dpad_off;
+      // reflect: full correlation (offset 2) -> padded gradient -> fold; zero pad: the plain pad-1 correlation
+      int rcw = run_wino_conv(d->algo, d->B, d->Cout, d->OH, d->OW, d->Cin, GH, GW, rf ? 2 : 1, false, gy, U, nullptr,
+                              HIM_ACT_NONE, 0.f, rf ? dpadw : out, wsf + p.scratch_off, st, p.wino_fold, true);
+      if (rcw || !rf) return rcw;
+      hipLaunchKernelGGL(reflect_fold_kernel, dim3(cdiv((long long)d->H * d->W, 256), d->B * d->Cin), dim3(256), 0, st,
+                         (const float*)dpadw, out, d->B * d->Cin, d->H, d->W, 1, 1, (size_t)0);
+      return check_launch("reflect_fold");
     }
-    const bool fold = wino_dgrad_fold(d);
-    const bool rf = d->pad_mode == HIM_PAD_REFLECT && !fold;
-    const int GH = rf ? d->H + 2 : d->H, GW = rf ? d->W + 2 : d->W;
-    float* wsv = U + (size_t)16 * d->Cin * d->Cout;
-    float* dpadw = wsv + wino_conv_floats(d->B, d->Cout, d->Cin, GH, GW);
-    // reflect: full correlation (offset 2) -> padded gradient -> fold; zero pad: the plain pad-1 correlation
-    int rcw = run_wino_conv(d->algo, d->B, d->Cout, d->OH, d->OW, d->Cin, GH, GW, rf ? 2 : 1, false, gy, panel ? panel : U,
-                            nullptr, HIM_ACT_NONE, 0.f, rf ? dpadw : out, wsv, st, fold, true);
-    if (rcw || !rf) return rcw;
-    hipLaunchKernelGGL(reflect_fold_kernel, dim3(cdiv((long long)d->H * d->W, 256), d->B * d->Cin), dim3(256), 0, st,
-                       (const float*)dpadw, out, d->B * d->Cin, d->H, d->W, 1, 1, (size_t)0);
-    return check_launch("reflect_fold");
+    default: break;
   }
-  float* Wt = panel ? (float*)panel : (float*)ws;
-  const bool dfold = dfold_ok(d);
-  const bool refl = d->pad_mode == HIM_PAD_REFLECT && !dfold;
-  const bool fast = use_fast(d->algo, d->Cin, d->Cout);
+  float* Wt = panel ? (float*)panel : wsf;
+  const bool dfold = p.dfold, refl = p.refl_pad, fast = p.fast;
   GConvP g;
   memset(&g, 0, sizeof(g));
   WTransP wt;
   memset(&wt, 0, sizeof(wt));
   wt.W = w;
   const int IH = refl ? d->H + 2 * d->pad : d->H, IW = refl ? d->W + 2 * d->pad : d->W;
-  long long nw = setup_dgrad(g, wt, d->Cout, d->Cin, d->KH, d->KW, d->stride, refl ? 0 : d->pad, IH, IW, Wt);
+  const long long nw = setup_dgrad(g, wt, d->Cout, d->Cin, d->KH, d->KW, d->stride, refl ? 0 : d->pad, IH, IW, Wt);
   const bool holes = (g.kno_finish & 2) != 0;  // stride phases without a filter tap: zero gradient there
   g.kno_finish = 0;
   if (holes && (bias || act != HIM_ACT_NONE))
@@ -1169,19 +1204,13 @@ static int run_dgrad(const HimConv2d* d, const float* gy, const float* w, float*
       g.ph[q].C2p = Cop;
       off += t2.ph[q].total;
     }
-    nw = off;
     g.fast = 1;
   }
-  float* dpad = (float*)ws + ((nw + 63) / 64) * 64;
-  if (fast && g.nphase == 1) {
-    const int ks = dgrad_ksplit(d);
-    if (ks > 1) {
-      const size_t outn = (size_t)d->B * d->Cin * IH * IW;
-      g.ksplit = ks;
-      const size_t extn = dfold ? (size_t)d->B * d->Cout * (d->OH + 2) * (d->OW + 2) : 0;
-      g.kpart = dpad + (refl ? ((outn + 63) / 64) * 64 : ((extn + 63) / 64) * 64);
-      g.kno_finish = refl ? 1 : 0;
-    }
+  float* dpad = wsf + p.dpad_off;
+  if (p.ksplit > 1) {
+    g.ksplit = p.ksplit;
+    g.kpart = wsf + p.kpart_off;
+    g.kno_finish = refl ? 1 : 0;
   }
   g.src = dfold ? dpad : gy;
   g.dst = refl ? dpad : out;
@@ -1247,12 +1276,10 @@ static int run_dgrad(const HimConv2d* d, const float* gy, const float* w, float*
   rc = launch_gconv(d->algo, g, st);
   if (rc) return rc;
   if (refl) {
-    const long long tot = (long long)d->B * d->Cin * d->H * d->W;
     const bool slabs = g.ksplit > 1;
-    (void)tot;
     hipLaunchKernelGGL(reflect_fold_kernel, dim3(cdiv((long long)d->H * d->W, 256), d->B * d->Cin), dim3(256), 0, st,
                        (const float*)(slabs ? g.kpart : dpad), out, d->B * d->Cin, d->H, d->W, d->pad,
-                       slabs ? g.ksplit : 1, (size_t)d->B * d->Cin * IH * IW);
+                       slabs ? g.ksplit : 1, p.pad_floats);
     rc = check_launch("reflect_fold");
   }
   return rc;
@@ -1354,7 +1381,7 @@ int him_winograd_gemm(const float* a, const float* b, float* c, int M, int K, in
   return wino_batched_gemm(algo ? *algo : z, a, b, c, M, K, N, (hipStream_t)stream);
 }
 
-size_t him_conv2d_fwd_ws(const HimConv2d* d) { return d ? fprop_ws_bytes(d) : 0; }
+size_t him_conv2d_fwd_ws(const HimConv2d* d) { return d ? plan_fprop(d).ws_bytes : 0; }
 
 int him_conv2d_fwd(const HimConv2d* d, const float* x, const float* w, const float* bias, float* y, void* ws,
                    size_t ws_bytes, void* stream) {
@@ -1363,7 +1390,7 @@ int him_conv2d_fwd(const HimConv2d* d, const float* x, const float* w, const flo
   return run_fprop(d, x, w, bias, y, ws, ws_bytes, (hipStream_t)stream);
 }
 
-int him_conv2d_in_act_fused(const HimConv2d* d) { return (d && !check_conv(d) && in_act_slab_ok(d)) ? 1 : 0; }
+int him_conv2d_in_act_fused(const HimConv2d* d) { return (d && !check_conv(d) && plan_fprop(d).in_act_slab) ? 1 : 0; }
 
 int him_conv2d_in_act_fwd(const HimConv2d* d, const float* x, const float* w, const void* panel, const float* bias,
                           float* y_raw, const float* residual, float* z, float* mean, float* rstd, float eps, int act,
@@ -1372,7 +1399,7 @@ int him_conv2d_in_act_fwd(const HimConv2d* d, const float* x, const float* w, co
   if (rc) return rc;
   if (d->act != HIM_ACT_NONE) return fail(HIM_E_INVALID, "conv_in_act: the activation follows the norm (descriptor act must be none)");
   if (!y_raw || !z || !mean || !rstd) return fail(HIM_E_INVALID, "conv_in_act: null output");
-  if (panel && !fprop_panel_floats(d)) return fail(HIM_E_INVALID, "conv_in_act: no panel for this descriptor");
+  if (panel && !plan_fprop(d).panel_floats) return fail(HIM_E_INVALID, "conv_in_act: no panel for this descriptor");
   hipStream_t st = (hipStream_t)stream;
   FpropDefer df;
   df.slabs = nullptr;
@@ -1386,7 +1413,7 @@ int him_conv2d_in_act_fwd(const HimConv2d* d, const float* x, const float* w, co
   return him_instnorm_fwd(y_raw, residual, z, mean, rstd, planes, hw, eps, act, slope, stream);
 }
 
-size_t him_conv2d_bwd_data_ws(const HimConv2d* d) { return d ? dgrad_ws_bytes(d) : 0; }
+size_t him_conv2d_bwd_data_ws(const HimConv2d* d) { return d ? plan_dgrad(d, false).ws_bytes : 0; }
 
 int him_conv2d_bwd_data(const HimConv2d* d, const float* dy, const float* w, float* dx, void* ws,
                         size_t ws_bytes, void* stream) {
@@ -1397,7 +1424,7 @@ int him_conv2d_bwd_data(const HimConv2d* d, const float* dy, const float* w, flo
 
 size_t him_conv2d_panel_bytes(const HimConv2d* d, int kind) {
   if (!d || check_conv(d)) return 0;
-  return (kind == HIM_PANEL_FWD ? fprop_panel_floats(d) : dgrad_panel_floats(d)) * sizeof(float);
+  return (kind == HIM_PANEL_FWD ? plan_fprop(d) : plan_dgrad(d, false)).panel_floats * sizeof(float);
 }
 
 // Which regrouping of the weights the panel of (descriptor, kind) holds: 0 none (the kernel reads the raw weights), 1 the
@@ -1406,19 +1433,13 @@ size_t him_conv2d_panel_bytes(const HimConv2d* d, int kind) {
 // SAME weight called with another batch / plane size may land on another layout (F(4x4) needs H, W % 4 == 0 and >= 64 real
 // tiles; the tiny-head forms switch on the output size), so a cache of built panels must key on it.
 int him_conv2d_panel_layout(const HimConv2d* d, int kind) {
-  if (!d || check_conv(d)) return 0;
-  if (kind == HIM_PANEL_FWD) {
-    if (!fprop_panel_floats(d)) return 0;
-    return wino4_fwd_ok(d) ? 4 : wino_fused_fwd_ok(d) ? 3 : wino_fwd_ok(d) ? 2 : 1;
-  }
-  if (kind != HIM_PANEL_BWD_DATA || !dgrad_panel_floats(d)) return 0;
-  return wino4_dgrad_ok(d) ? 4 : wino_fused_dgrad_ok(d) ? 3 : wino_dgrad_ok(d) ? 2 : 1;
+  if (!d || check_conv(d) || (kind != HIM_PANEL_FWD && kind != HIM_PANEL_BWD_DATA)) return 0;
+  const ConvPlan p = kind == HIM_PANEL_FWD ? plan_fprop(d) : plan_dgrad(d, false);
+  return p.panel_floats ? (int)p.family : 0;
 }
 
 int him_conv2d_bwd_data_shares_fwd_panel(const HimConv2d* d) {
-  if (!d || check_conv(d)) return 0;
-  if (wino4_fwd_ok(d) || wino4_dgrad_ok(d)) return 0;
-  return (!wino_fused_dgrad_ok(d) && wino_dgrad_ok(d) && !wino_fused_fwd_ok(d) && wino_fwd_ok(d)) ? 1 : 0;
+  return (d && !check_conv(d) && plan_fprop(d).family == CONV_WINO && plan_dgrad(d, false).family == CONV_WINO) ? 1 : 0;
 }
 
 int him_conv2d_panel_build(const HimConv2d* d, int kind, const float* w, void* panel, size_t panel_bytes,
@@ -1426,7 +1447,7 @@ int him_conv2d_panel_build(const HimConv2d* d, int kind, const float* w, void* p
   int rc = check_conv(d);
   if (rc) return rc;
   if (kind == HIM_PANEL_FWD) {
-    if (!fprop_panel_floats(d)) return fail(HIM_E_UNSUPPORTED, "this conv's forward reads the raw weights: no panel");
+    if (!plan_fprop(d).panel_floats) return fail(HIM_E_UNSUPPORTED, "this conv's forward reads the raw weights: no panel");
     return run_fprop(d, nullptr, w, nullptr, nullptr, panel, panel_bytes, (hipStream_t)stream, nullptr, true);
   }
   if (kind != HIM_PANEL_BWD_DATA) return fail(HIM_E_INVALID, "panel kind %d", kind);
@@ -1438,7 +1459,7 @@ int him_conv2d_fwd_panel(const HimConv2d* d, const float* x, const void* panel, 
                          size_t ws_bytes, void* stream) {
   int rc = check_conv(d);
   if (rc) return rc;
-  if (!panel || !fprop_panel_floats(d)) return fail(HIM_E_INVALID, "conv fwd: no panel for this descriptor");
+  if (!panel || !plan_fprop(d).panel_floats) return fail(HIM_E_INVALID, "conv fwd: no panel for this descriptor");
   return run_fprop(d, x, nullptr, bias, y, ws, ws_bytes, (hipStream_t)stream, (const float*)panel);
 }
 
@@ -1475,43 +1496,34 @@ int him_conv2d_bwd_data_gated(const HimConv2d* d, const float* dy, const float* 
 }
 
 // ---- kept Winograd input transform (include/him.h) ----
-static bool fwd_keep_ok(const HimConv2d* d) {
-  if (check_conv(d) || wino4_fwd_ok(d) || wino_fused_fwd_ok(d) || !wino_fwd_ok(d)) return false;
-  if (!wino_wgrad_ok(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad, d->H, d->W) || d->OH != d->H || d->OW != d->W)
-    return false;
-  const WinoGeom g = wino_geom(d->B, d->Cin, d->H, d->W, d->OH, d->OW, 1);
-  return !algo_off(d->algo, HIM_ALGO_NO_BGEMM) && bgemm_shape_ok(d->Cout, g.Tp, d->Cin, 16);
-}
-size_t him_conv2d_fwd_keep_bytes(const HimConv2d* d) {
-  if (!d || !fwd_keep_ok(d)) return 0;
-  const WinoGeom g = wino_geom(d->B, d->Cin, d->H, d->W, d->OH, d->OW, 1);
-  return (size_t)16 * d->Cin * g.Tp * sizeof(float);
-}
+static bool fwd_keep_ok(const HimConv2d* d) { return !check_conv(d) && plan_fprop(d).keep_floats != 0; }
+size_t him_conv2d_fwd_keep_bytes(const HimConv2d* d) { return (d && fwd_keep_ok(d)) ? plan_fprop(d).keep_floats * sizeof(float) : 0; }
 int him_conv2d_fwd_panel_keep(const HimConv2d* d, const float* x, const void* panel, const float* bias, float* y, float* keep,
                               void* ws, size_t ws_bytes, void* stream) {
   int rc = check_conv(d);
   if (rc) return rc;
-  if (!panel || !fprop_panel_floats(d)) return fail(HIM_E_INVALID, "conv fwd: no panel for this descriptor");
+  if (!panel || !plan_fprop(d).panel_floats) return fail(HIM_E_INVALID, "conv fwd: no panel for this descriptor");
   if (keep && !fwd_keep_ok(d)) return fail(HIM_E_UNSUPPORTED, "conv fwd: this layer has no transformed input to keep");
   return run_fprop(d, x, nullptr, bias, y, ws, ws_bytes, (hipStream_t)stream, (const float*)panel, false, keep);
+}
+// dw from x -- or from the forward's kept transform of it -- then dbias behind the slab region
+static int conv_bwd_weight(const HimConv2d* d, const float* x, const float* keep, const float* dy, float* dw, float* dbias,
+                           int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (dw) {
+    int rc = run_wgrad(d->algo, dy, x, dw, d->Cout, d->Cin, d->B, d->H, d->W, d->OH, d->OW, d->KH, d->KW, d->stride, d->pad,
+                       d->pad_mode, accumulate, ws, ws_bytes, st, keep);
+    if (rc) return rc;
+  }
+  if (!dbias) return HIM_OK;
+  const size_t off = wgrad_slab_bytes(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->B * d->OH * d->OW, conv_wino_wgrad_floats(d));
+  return run_bias_grad_behind(dy, dbias, d->B, d->Cout, d->OH * d->OW, accumulate, ws, ws_bytes, off, st);
 }
 int him_conv2d_bwd_weight_kept(const HimConv2d* d, const float* keep, const float* dy, float* dw, float* dbias, int accumulate,
                                void* ws, size_t ws_bytes, void* stream) {
   int rc = check_conv(d);
   if (rc) return rc;
   if (!keep || !fwd_keep_ok(d)) return fail(HIM_E_INVALID, "conv bwd_weight_kept: no kept transform for this descriptor");
-  if (dw) {
-    rc = run_wgrad(d->algo, dy, nullptr, dw, d->Cout, d->Cin, d->B, d->H, d->W, d->OH, d->OW, d->KH, d->KW, d->stride, d->pad,
-                   d->pad_mode, accumulate, ws, ws_bytes, (hipStream_t)stream, keep);
-    if (rc) return rc;
-  }
-  if (dbias) {
-    const size_t off = wgrad_slab_bytes(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->B * d->OH * d->OW, conv_wino_wgrad_floats(d));
-    if (ws_bytes < off) return fail(HIM_E_WORKSPACE, "bwd_weight ws too small");
-    rc = run_bias_grad(dy, dbias, d->B, d->Cout, d->OH * d->OW, accumulate, (char*)ws + off, ws_bytes - off,
-                       (hipStream_t)stream);
-  }
-  return rc;
+  return conv_bwd_weight(d, nullptr, keep, dy, dw, dbias, accumulate, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t him_conv2d_bwd_weight_ws(const HimConv2d* d) {
@@ -1522,20 +1534,8 @@ int him_conv2d_bwd_weight(const HimConv2d* d, const float* x, const float* dy, f
                           int accumulate, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_conv(d);
   if (rc) return rc;
-  if (dw) {
-    rc = run_wgrad(d->algo, dy, x, dw, d->Cout, d->Cin, d->B, d->H, d->W, d->OH, d->OW, d->KH, d->KW, d->stride, d->pad,
-                   d->pad_mode, accumulate, ws, ws_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  if (dbias) {
-    const size_t off = wgrad_slab_bytes(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->B * d->OH * d->OW, conv_wino_wgrad_floats(d));
-    if (ws_bytes < off) return fail(HIM_E_WORKSPACE, "bwd_weight ws too small");
-    rc = run_bias_grad(dy, dbias, d->B, d->Cout, d->OH * d->OW, accumulate, (char*)ws + off, ws_bytes - off,
-                       (hipStream_t)stream);
-  }
-  return rc;
+  return conv_bwd_weight(d, x, nullptr, dy, dw, dbias, accumulate, ws, ws_bytes, (hipStream_t)stream);
 }
-
 
 size_t him_conv2d_onehot_fwd_ws(const HimConv2d* d, int n_onehot) {
   return (d && !check_conv(d) && onehot_ok(d, n_onehot)) ? onehot_fwd_ws_bytes(d, n_onehot) : 0;
@@ -1565,7 +1565,7 @@ static int onehot_fwd_impl(const HimConv2d* d, const float* label, int n_onehot,
     hipLaunchKernelGGL(onehot_dense_w_kernel, dim3(cdiv((long long)d->Cout * Cd * KK, 256)), dim3(256), 0, st,
                        (float*)w, wd, d->Cout, d->Cin, NC, KK, 0, 0);
     const HimConv2d dd = onehot_dense_desc(d, NC);
-    rc = run_fprop(&dd, x_dense ? x : xd, wd, bias, y, cws, fprop_ws_bytes(&dd), st);
+    rc = run_fprop(&dd, x_dense ? x : xd, wd, bias, y, cws, plan_fprop(&dd).ws_bytes, st);
     if (rc) return rc;
   }
   OneHotP p;
@@ -1720,7 +1720,7 @@ int him_conv2d_onehot_bwd_weight_part(const HimConv2d* d, const float* label, in
 size_t him_deconv2d_fwd_ws(const HimDeconv2d* t) {
   HimConv2d c;
   if (adjoint_of(t, &c)) return 0;
-  return dgrad_ws_bytes(&c);
+  return plan_dgrad(&c, false).ws_bytes;
 }
 
 int him_deconv2d_fwd(const HimDeconv2d* t, const float* x, const float* w, const float* bias, float* y,
@@ -1735,7 +1735,7 @@ int him_deconv2d_fwd(const HimDeconv2d* t, const float* x, const float* w, const
 size_t him_deconv2d_bwd_data_ws(const HimDeconv2d* t) {
   HimConv2d c;
   if (adjoint_of(t, &c)) return 0;
-  return fprop_ws_bytes(&c);
+  return plan_fprop(&c).ws_bytes;
 }
 
 int him_deconv2d_bwd_data(const HimDeconv2d* t, const float* dy, const float* w, float* dx, void* ws, size_t ws_bytes,
@@ -1776,7 +1776,7 @@ int him_deconv2d_bwd_data_panel(const HimDeconv2d* t, const float* dy, const voi
   HimConv2d c;
   int rc = adjoint_of(t, &c);
   if (rc) return rc;
-  if (!panel || !fprop_panel_floats(&c)) return fail(HIM_E_INVALID, "deconv bwd_data: no panel for this descriptor");
+  if (!panel || !plan_fprop(&c).panel_floats) return fail(HIM_E_INVALID, "deconv bwd_data: no panel for this descriptor");
   return run_fprop(&c, dy, nullptr, nullptr, dx, ws, ws_bytes, (hipStream_t)stream, (const float*)panel);
 }
 
@@ -1797,13 +1797,9 @@ int him_deconv2d_bwd_weight(const HimDeconv2d* t, const float* x, const float* d
                    accumulate, ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
   }
-  if (dbias) {
-    const size_t off = wgrad_slab_bytes(c.algo, c.Cout, c.Cin, c.KH, c.KW, c.B * c.OH * c.OW);
-    if (ws_bytes < off) return fail(HIM_E_WORKSPACE, "bwd_weight ws too small");
-    rc = run_bias_grad(dy, dbias, t->B, t->Cout, t->OH * t->OW, accumulate, (char*)ws + off, ws_bytes - off,
-                       (hipStream_t)stream);
-  }
-  return rc;
+  if (!dbias) return HIM_OK;
+  return run_bias_grad_behind(dy, dbias, t->B, t->Cout, t->OH * t->OW, accumulate, ws, ws_bytes,
+                              wgrad_slab_bytes(c.algo, c.Cout, c.Cin, c.KH, c.KW, c.B * c.OH * c.OW), (hipStream_t)stream);
 }
 
 }  // extern "C"

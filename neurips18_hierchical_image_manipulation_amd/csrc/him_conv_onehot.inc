@@ -330,7 +330,7 @@ static size_t onehot_fwd_ws_bytes(const HimConv2d* d, int NC) {
   if (Cd > 0) {
     const HimConv2d dd = onehot_dense_desc(d, NC);
     n += ((size_t)d->B * Cd * d->H * d->W + 63) / 64 * 64 + ((size_t)d->Cout * Cd * KK + 63) / 64 * 64;
-    return n * sizeof(float) + fprop_ws_bytes(&dd) + 256;
+    return n * sizeof(float) + plan_fprop(&dd).ws_bytes + 256;
   }
   return n * sizeof(float) + 256;
 }

@@ -128,6 +128,7 @@ static HimConv2d resblock_conv_desc(const HimResBlock* d) {
   c.B = d->B; c.Cin = d->C; c.Cout = d->C; c.H = d->H; c.W = d->W; c.OH = d->H; c.OW = d->W;
   c.KH = c.KW = 3; c.stride = 1; c.pad = 1; c.pad_mode = HIM_PAD_REFLECT; c.act = HIM_ACT_NONE;
   c.algo = d->algo;
+  c.algo.disable &= ~HIM_ALGO_WINO4_TRAIN_FWD;   // the block runs its own F(2x2) pipeline whatever the layerwise forward would take
   return c;
 }
 static bool resblock_ok(const HimResBlock* d) {
@@ -136,7 +137,8 @@ static bool resblock_ok(const HimResBlock* d) {
   if (check_conv(&c)) return false;
   // the separate-transform Winograd pipeline in all three directions (the fused single-launch kernel owns <= 512 channels),
   // the reflect gradient folded into the border patches (even planes), a plane that fits one workgroup's LDS
-  return wino_fwd_ok(&c) && !wino_fused_fwd_ok(&c) && wino_dgrad_ok(&c) && wino_dgrad_fold(&c) &&
+  const ConvPlan g = plan_dgrad(&c, false);
+  return plan_fprop(&c).family == CONV_WINO && g.family == CONV_WINO && g.wino_fold &&
          wino_wgrad_ok(d->algo, d->C, d->C, 3, 3, 1, 1, d->H, d->W) && d->H * d->W <= 4096;
 }
 static size_t resblock_ws_floats(const HimResBlock* d) {   // V + M of one convolution

@@ -3,7 +3,7 @@ the guarded C-ABI harness of tests/abi_harness.py against float64 -- see tests/R
 
 One table (ROWS): shape, HimAlgo overrides, passes, and the relation of the override to the base selection on the same
 inputs -- 'identical' (the code documents bit-identity: torch.equal), 'differs' (another summation order: not equal, which
-proves the knob reached the library) or 'any' (with the reason).  Line numbers cite csrc/ of this commit."""
+proves the knob reached the library) or 'any' (with the reason).  Citations name the functions of csrc/ that hold the choice."""
 import ctypes
 import os
 
@@ -22,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIM_H = os.path.join(HERE, '..', 'include', 'him.h')
 OUT = os.path.join(REPORT_DIR, 'conv_abi_rows.jsonl')      # next to the model tests' trajectory reports
 ALL3 = ('fwd', 'bwd_data', 'bwd_weight')
-NOWINO = {'wino_min_c': -1}          # him_common.h:123 / him_conv.hip:867: every Winograd form off -> the direct form
+NOWINO = {'wino_min_c': -1}          # him_common.h algo_wino_min_c / him_conv.hip wino_fused_ok: every Winograd form off -> the direct form
 WINO16 = {'wino_min_c': 16}          # separate-transform F(2x2) from 16 channels (the setting of WINO_CASES)
 
 
@@ -48,7 +48,7 @@ def bound_for(lib, case, a, what):
     d = case.desc(a)
     wide = 5e-5 if case.Cin >= 512 else 2e-5
     if what == 'bwd_weight':
-        # him_conv.hip:427 wino_wgrad_ok: the F(2x2) layers with both channel counts % 128 == 0
+        # him_conv.hip wino_wgrad_ok: the F(2x2) layers with both channel counts % 128 == 0
         a2 = H.algo(**a.as_dict())       # the forward's F(4x4) marks do not move the weight gradient
         a2.disable &= ~(A.ALGO_FROZEN_WEIGHTS | A.ALGO_WINO4_TRAIN_FWD)
         wino = lib.him_conv2d_panel_layout(ctypes.byref(case.desc(a2)), 0) == 2
@@ -90,9 +90,9 @@ S2BIG = (2, 136, 16, 32, 160, 3, 2, 1, 'zero', 'none')          # stride 2: the 
 PATCH = (2, 64, 17, 33, 128, 4, 2, 2, 'zero', 'none')           # CONV_CASES: PatchGAN block (split-K slabs feed the norm)
 DECONV = (2, 136, 4, 6, 72)                                     # DECONV_CASES: four phases, M = 72 fwd / 136 dgrad
 
-# tile_nb: him_conv.hip:208-245 -- read for M > 64 on the fast path only.  Every tile shape walks K in the same order, so
+# tile_nb: him_conv.hip launch_gconv -- read for M > 64 on the fast path only.  Every tile shape walks K in the same order, so
 # the sums may or may not move: 'any' (the code promises neither); error bounds and guards are the check.
-TILE_WHY = 'him_conv.hip:230-245: the tile shape changes the launch grid, the K loop order is not documented either way'
+TILE_WHY = 'him_conv.hip launch_gconv: the tile shape changes the launch grid, the K loop order is not documented either way'
 for code in range(1, 8):
     row('tile_nb=%d tails' % code, TAILS, ('fwd', 'bwd_data'), dict(NOWINO, tile_nb=code), 'any', NOWINO, TILE_WHY)
 for code in (1, 2, 3, 5, 6, 7):
@@ -104,8 +104,8 @@ for code in (1, 2, 4, 5, 6, 7):
     row('tile_nb=%d stride-2 phases' % code, S2BIG, ('fwd', 'bwd_data'), {'tile_nb': code}, 'any', None, TILE_WHY)
     row('tile_nb=%d deconv' % code, DECONV, ('fwd', 'bwd_data'), {'tile_nb': code}, 'any', None, TILE_WHY)
 
-# tile_wb: him_conv.hip:208 p.wbatch -- the batched GEMM of the separate-transform Winograd layers when it runs on the conv
-# kernel: always under NO_BGEMM (him_conv.hip:447), and without it where 16 * (M/128) * (N/128) < 512.
+# tile_wb: him_conv.hip launch_gconv, p.wbatch -- the batched GEMM of the separate-transform Winograd layers when it runs on the conv
+# kernel: always under NO_BGEMM (wino_batched_gemm), and without it where 16 * (M/128) * (N/128) < 512.
 W128 = (1, 128, 6, 10, 128, 'reflect')       # WINO_CASES: 15 tiles -> 128 GEMM columns, 16 GEMM tiles: conv kernel either way
 W256 = (2, 128, 8, 8, 256, 'zero')           # WINO_CASES: rectangular
 W512 = (16, 512, 16, 16, 512, 'zero')        # WINO_CASES: 1024 columns, 16*4*8 = 512 tiles: the LDS-DMA GEMM unless NO_BGEMM
@@ -155,24 +155,24 @@ for c in (WG_M, WG_C, WG_99, WG_P):
                 {'wgrad_tile': tile, 'wgrad_splits': splits}, rel, None,
                 'him_conv_wgrad.inc:425-426: another tile, the same number of K slabs (%s vs %s)' % (got, base))
 
-# split-K: him_conv.hip:819-848 fast_ksplit; the default cap is 4
+# split-K: him_conv.hip fast_ksplit; the default cap is 4
 for over, rel in (({'disable': A.ALGO_NO_SPLITK}, 'differs'), ({'ksplit_max': 1}, 'differs'), ({'ksplit_max': 2}, 'any'),
                   ({'ksplit_max': 3}, 'any'), ({'ksplit_max': 8}, 'any')):
-    why = 'him_conv.hip:835-846: the cost model may pick the same factor under another cap'
+    why = 'him_conv.hip fast_ksplit: the cost model may pick the same factor under another cap'
     tag = ','.join('%s=%d' % kv for kv in over.items())
     row('%s conv' % tag, SPLITK, ('fwd', 'bwd_data'), dict(NOWINO, **over), rel, NOWINO, why)
     row('%s in_act' % tag, PATCH, ('fwd', 'in_act'), over, rel, None, why)
 
-# wino_tblock: him_conv.hip:423-426 "results are bit-identical"
+# wino_tblock: him_conv.hip wino_tblock "results are bit-identical"
 for tb in (64, 128, 256):
     for c in ((1, 48, 9, 13, 32, 'reflect'), W128):
         row('wino_tblock=%d %s' % (tb, 'x'.join(map(str, c[:5]))), wino(c), ALL3, dict(WINO16, wino_tblock=tb), 'identical', WINO16)
 
-# fused Winograd chunk: him_common.h:128 (anything but 4 is 8); him_conv.hip:875: chunk 4 also leaves the persistent kernel
+# fused Winograd chunk: him_common.h algo_wino_fused_chunk (anything but 4 is 8); him_conv.hip wino_fused2_ok: chunk 4 also leaves the persistent kernel
 FUSED = (2, 128, 16, 32, 128, 3, 1, 1, 'zero', 'relu')          # CONV_CASES: fused Winograd kernel, fwd + zero-pad dgrad
 row('wino_fused_chunk=8', FUSED, ('fwd', 'bwd_data'), {'wino_fused_chunk': 8}, 'identical')
 row('wino_fused_chunk=4', FUSED, ('fwd', 'bwd_data'), {'wino_fused_chunk': 4}, 'differs')
-# thresholds moved across the channel count (him_conv.hip:418-422, 865-870; him_conv_wino4.inc:196-202)
+# thresholds moved across the channel count (him_conv.hip wino_shape_ok, wino_fused_ok; him_conv_wino4.inc wino4_shape_ok)
 C32 = wino((2, 32, 16, 32, 32, 'reflect'))
 C256 = (1, 256, 8, 16, 256, 3, 1, 1, 'zero', 'relu')            # CONV_CASES "VGG mid": separate transforms by default (>= 256)
 row('wino_min_c=32 at 32 channels', C32, ALL3, {'wino_min_c': 32}, 'differs')
@@ -198,15 +198,15 @@ row('NO_WINO_FUSED2', FUSED, ('fwd', 'bwd_data'), {'disable': A.ALGO_NO_WINO_FUS
 # the disable bits the op tests never flipped, each at a shape (from CONV_CASES' comments) where it changes the kernel
 KERNEL_WHY = 'another kernel for the same sums; whether its order differs is not documented at %s'
 row('NO_DFOLD', (2, 16, 16, 32, 16, 3, 1, 1, 'reflect', 'none'), ('bwd_data',), {'disable': A.ALGO_NO_DFOLD}, 'any', None,
-    KERNEL_WHY % 'him_conv.hip:1036')
-row('NO_DFOLD split-K', SPLITK, ('bwd_data',), dict(NOWINO, disable=A.ALGO_NO_DFOLD), 'any', NOWINO, KERNEL_WHY % 'him_conv.hip:1036')
+    KERNEL_WHY % 'him_conv.hip plan_dgrad (dfold)')
+row('NO_DFOLD split-K', SPLITK, ('bwd_data',), dict(NOWINO, disable=A.ALGO_NO_DFOLD), 'any', NOWINO, KERNEL_WHY % 'him_conv.hip plan_dgrad (dfold)')
 row('WINO_PADDED_DGRAD', C32, ('bwd_data',), dict(WINO16, disable=A.ALGO_WINO_PADDED_DGRAD), 'any', WINO16,
-    KERNEL_WHY % 'him_conv.hip:1044')
+    KERNEL_WHY % 'him_conv.hip plan_dgrad (wino_fold)')
 row('WINO_PADDED_DGRAD 4x4', wino((2, 32, 4, 4, 32, 'reflect')), ('bwd_data',), dict(WINO16, disable=A.ALGO_WINO_PADDED_DGRAD),
-    'any', WINO16, KERNEL_WHY % 'him_conv.hip:1044')
+    'any', WINO16, KERNEL_WHY % 'him_conv.hip plan_dgrad (wino_fold)')
 for c in ((2, 20, 9, 70, 2, 3, 1, 1, 'zero', 'none'), (1, 12, 70, 9, 4, 5, 1, 2, 'reflect', 'none'),
           (2, 8, 12, 66, 4, 7, 1, 3, 'reflect', 'none')):
-    row('NO_SMALL_WIN %d' % c[5], c, ('bwd_weight',), {'disable': A.ALGO_NO_SMALL_WIN}, 'any', None, KERNEL_WHY % 'him_conv.hip:509')
+    row('NO_SMALL_WIN %d' % c[5], c, ('bwd_weight',), {'disable': A.ALGO_NO_SMALL_WIN}, 'any', None, KERNEL_WHY % 'him_conv.hip small_win_ok')
 for c in ((40, 16, 40, 70, 3, 7, 1, 3, 'reflect', 'none'), (34, 12, 33, 65, 4, 3, 1, 1, 'zero', 'none')):
     row('NO_FEWOUT_TILED %d' % c[5], c, ('fwd',), {'disable': A.ALGO_NO_FEWOUT_TILED}, 'any', None,
         KERNEL_WHY % 'him_conv_direct.inc:438')
@@ -217,7 +217,7 @@ row('NO_FEWIN_TILED fwd', (8, 4, 120, 250, 16, 7, 1, 3, 'zero', 'none'), ('fwd',
 row('NO_FEWIN_TILED dgrad', (8, 16, 130, 250, 2, 3, 1, 1, 'zero', 'none'), ('bwd_data',), {'disable': A.ALGO_NO_FEWIN_TILED}, 'any',
     None, KERNEL_WHY % 'him_conv_direct.inc:593')
 row('NO_FEWIN_FOLD', (8, 32, 128, 250, 3, 7, 1, 3, 'reflect', 'none'), ('bwd_data',), {'disable': A.ALGO_NO_FEWIN_FOLD}, 'any', None,
-    KERNEL_WHY % 'him_conv.hip:1230')
+    KERNEL_WHY % 'him_conv.hip run_dgrad (fewin fold)')
 row('NO_FEWIN_REFLECT', (2, 3, 37, 150, 64, 7, 1, 3, 'reflect', 'none'), ('fwd',), {'disable': A.ALGO_NO_FEWIN_REFLECT}, 'any', None,
     KERNEL_WHY % 'him_conv_direct.inc:601')
 for c in ((2, 96, 37, 150, 3, 7, 1, 3, 'zero', 'none'), (2, 4, 20, 140, 32, 5, 1, 2, 'zero', 'none')):
@@ -225,10 +225,10 @@ for c in ((2, 96, 37, 150, 3, 7, 1, 3, 'zero', 'none'), (2, 4, 20, 140, 32, 5, 1
         KERNEL_WHY % 'him_wgrad_fewch.inc:201')
 for c in (TAILS, PATCH, (3, 128, 8, 10, 256, 4, 1, 2, 'zero', 'none')):
     row('GENERIC_CONV %s' % 'x'.join(map(str, c[:5])), c, ALL3, dict(NOWINO, disable=A.ALGO_GENERIC_CONV), 'any', NOWINO,
-        KERNEL_WHY % 'him_conv.hip:104, him_conv_wgrad.inc:421')
-row('GENERIC_CONV deconv', DECONV, ALL3, {'disable': A.ALGO_GENERIC_CONV}, 'any', None, KERNEL_WHY % 'him_conv.hip:104')
-row('NO_BGEMM', wino(W512), ALL3, {'disable': A.ALGO_NO_BGEMM}, 'any', None, KERNEL_WHY % 'him_conv.hip:447')
-# him_resblock.inc:134 is the only reader of the bit: the layerwise path (the plain conv entry points) must not move
+        KERNEL_WHY % 'him_conv.hip use_fast, him_conv_wgrad.inc:421')
+row('GENERIC_CONV deconv', DECONV, ALL3, {'disable': A.ALGO_GENERIC_CONV}, 'any', None, KERNEL_WHY % 'him_conv.hip use_fast')
+row('NO_BGEMM', wino(W512), ALL3, {'disable': A.ALGO_NO_BGEMM}, 'any', None, KERNEL_WHY % 'him_conv.hip wino_batched_gemm')
+# him_resblock.inc resblock_ok is the only reader of the bit: the layerwise path (the plain conv entry points) must not move
 row('NO_RESBLOCK_FUSED layerwise', wino(W128), ALL3, dict(WINO16, disable=A.ALGO_NO_RESBLOCK_FUSED), 'identical', WINO16)
 
 EXTRA_ROWS = [{'name': 'NO_ONEHOT_RLE (test_onehot_weight_gradient_per_pixel_and_per_run)', 'over': {'disable': A.ALGO_NO_ONEHOT_RLE}}]
@@ -309,7 +309,7 @@ def test_refused_calls_write_nothing(c):
 
 # --------------------------------------------------------------------------------------- him_winograd_gemm on its own
 GEMM = [
-    # M, K, N, tile_wb, NO_BGEMM -- him_conv.hip:219-245 with maxN = 16 * N, tiles128 = 16 * N/128 * ceil(M/128)
+    # M, K, N, tile_wb, NO_BGEMM -- him_conv.hip launch_gconv with maxN = 16 * N, tiles128 = 16 * N/128 * ceil(M/128)
     (128, 32, 128, 0, 0), (136, 48, 256, 0, 0),                  # default tile, M tail
     (128, 16, 8192, A.TILE_128x256, 1),                          # 128x256 eligible: N % 256 == 0, tiles256 = 512
     (128, 32, 256, A.TILE_128x256, 1), (128, 32, 384, A.TILE_128x256, 1),   # not eligible: tiles256 = 16; N % 256 != 0
