@@ -174,6 +174,14 @@ int him_deconv2d_bwd_data(const HimDeconv2d* d, const float* dy, const float* w,
 size_t him_deconv2d_bwd_weight_ws(const HimDeconv2d* d);
 int him_deconv2d_bwd_weight(const HimDeconv2d* d, const float* x, const float* dy, float* dw, float* dbias,
                             int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* Diagnostics (pure host functions, no GPU): the plan him_conv2d_bwd_weight / him_deconv2d_bwd_weight run for a descriptor.
+ * family: 0 Winograd F(2x2), 1 few-channel MFMA head (Cout <= 4), 2 few-channel MFMA stem (Cin <= 4), 3 small-window,
+ * 4 small, 5 fast split-K GEMM, 6 generic split-K GEMM.  need_bytes: the workspace bytes that family touches, never more
+ * than the slab region (*_bwd_weight_ws minus the dbias scratch behind it).  splits: partial results summed in fixed
+ * order (split-K slabs / slices / slots / workgroups; 1: none).  tile_m x tile_n: the GEMM tile of families 5 and 6, else 0.
+ * Any out pointer may be NULL.  Returns the descriptor's error code, like the call itself. */
+int him_conv2d_bwd_weight_plan(const HimConv2d* d, int* family, size_t* need_bytes, int* splits, int* tile_m, int* tile_n);
+int him_deconv2d_bwd_weight_plan(const HimDeconv2d* d, int* family, size_t* need_bytes, int* splits, int* tile_m, int* tile_n);
 
 /* ---------------------------------------------------------------------------------------------
  * box2mask building blocks (second hot path, SURVEY 8 row a18: models/MaskTwoStreamConvSwitch_NET.py,

@@ -72,6 +72,9 @@ _SIGS = {
     'him_deconv2d_bwd_data': (c_int, [_DECONV, P, P, P, P, c_size_t, P]),
     'him_deconv2d_bwd_weight_ws': (c_size_t, [_DECONV]),
     'him_deconv2d_bwd_weight': (c_int, [_DECONV, P, P, P, P, c_int, P, c_size_t, P]),
+    # diagnostics: (descriptor, &family, &need_bytes, &splits, &tile_m, &tile_n)
+    'him_conv2d_bwd_weight_plan': (c_int, [_CONV, C.POINTER(c_int), C.POINTER(c_size_t)] + [C.POINTER(c_int)] * 3),
+    'him_deconv2d_bwd_weight_plan': (c_int, [_DECONV, C.POINTER(c_int), C.POINTER(c_size_t)] + [C.POINTER(c_int)] * 3),
     'him_algo_resolve': (None, [_ALGO, _ALGO]),
     'him_algo_from_env': (None, [_ALGO]),
     'him_conv2d_onehot_fwd_ws': (c_size_t, [_CONV, c_int]),

@@ -505,130 +505,187 @@ static int run_wino_conv(const HimAlgo& a, int B, int Csrc, int H, int W, int Mo
 
 #include "him_wgrad_fewch.inc"
 
-static const int SMALL_WIN_SLOTS = 256;
-static bool small_win_ok(const HimAlgo& a, int M, int KH, int KW, int stride, int pad, int H, int W, int OH, int OW) {
-  return !algo_off(a, HIM_ALGO_NO_SMALL_WIN) && M <= 4 && KH == KW && (KH == 3 || KH == 5 || KH == 7) && stride == 1 && pad == KH / 2 && OH == H && OW == W &&
-         H > pad && W > pad;
+// ---- the weight-gradient plan ------------------------------------------------------------------------------------------
+// Which family computes dW[M][C*KH*KW] from dy[B][M][OH][OW] and x[B][C][H][W], its launch configuration and its workspace:
+// a pure function of (HimAlgo, shape, allow_wino) and the ONLY place this selection is written down -- run_wgrad, the
+// *_bwd_weight_ws queries, the dbias offsets and the *_bwd_weight_plan diagnostics read it.  Families are tested in the order
+// of the enum.  A predicate has a CLASS part (channels, kernel: *_class) and a GEOMETRY part (stride, padding, plane): the
+// family runs where both hold; the reported slab region covers every family the class admits (sizes ignore the geometry).
+enum WGradFamily { WGRAD_WINO, WGRAD_HEAD, WGRAD_STEM, WGRAD_SMALL_WIN, WGRAD_SMALL, WGRAD_FAST, WGRAD_GENERIC };
+struct WGradShape {
+  int M, C, B, H, W, OH, OW, KH, KW, stride, pad, pad_mode;
+  int Np() const { return C * KH * KW; }
+  int Kdim() const { return B * OH * OW; }
+};
+static WGradShape wgrad_shape(const HimConv2d* d) {
+  return {d->Cout, d->Cin, d->B, d->H, d->W, d->OH, d->OW, d->KH, d->KW, d->stride, d->pad, d->pad_mode};
 }
-
+struct WGradPlan {
+  HimAlgo algo;
+  WGradShape s;
+  WGradFamily family;
+  int BM, BN;         // fast / generic: the tile (else 0)
+  int splits;         // partials in ws: split-K slabs (fast, generic), slices (small), slots (small-window), workgroups (head, stem)
+  int kchunk;         // small, fast, generic: reduction positions per split
+  bool reduce;        // a finish pass sums the partials into dw; false: the kernel writes (accumulates into) dw directly
+  size_t need_bytes;  // exactly what the family touches
+  size_t slab_bytes;  // the reported slab region; dbias scratch sits behind it
+};
+static const int SMALL_WIN_SLOTS = 256;
 static int small_wgrad_slices(int C, int Kdim) {
   int s = (2048 + C - 1) / C;
   const int maxs = cdiv(Kdim, 256 * 8);
   if (s > maxs) s = maxs;
   return s < 1 ? 1 : s;
 }
-static bool small_wgrad_ok(int M, int KH, int KW) { return M <= 4 && KH == KW && (KH == 7 || KH == 4 || KH == 3); }
-static size_t wgrad_slab_bytes(const HimAlgo& a, int M, int C, int KH, int KW, int Kdim, size_t wino_floats = 0) {
-  const int Np = C * KH * KW;
-  size_t slabs;
-  if (wino_floats) return ((wino_floats * sizeof(float) + 255) / 256) * 256;
-  const bool fewch_shape = !fewch_off(a) && KH == KW && (KH == 5 || KH == 7) &&
-                           ((M <= 4 && C >= 32 && (C % 32) == 0) || (C <= 4 && M >= 32 && (M % 32) == 0));
-  if (fewch_shape) {   // upper bound: the runner re-checks stride / padding / plane (else the kernels below, which need less)
-    slabs = fewch_ws_floats(M <= 4 ? C : M, KH) * sizeof(float);
-    if (small_wgrad_ok(M, KH, KW) || (M <= 4 && KH == 5))
-      slabs = std::max(slabs, (size_t)std::max(small_wgrad_slices(C, Kdim), SMALL_WIN_SLOTS) * M * Np * sizeof(float));
-    int BM2, BN2;
-    wgrad_tile(M, &BM2, &BN2);
-    const int s2 = wgrad_splits(M, Np, Kdim, BM2, BN2);
-    if (s2 > 1) slabs = std::max(slabs, (size_t)s2 * M * Np * sizeof(float));
-  } else if (small_wgrad_ok(M, KH, KW) || (M <= 4 && KH == KW && KH == 5)) {
-    slabs = (size_t)std::max(small_wgrad_slices(C, Kdim), SMALL_WIN_SLOTS) * M * Np * sizeof(float);
-  } else if (wgrad_fast_ok(a, M, C, 1, 4)) {  /* upper bound; the runner re-checks OH*OW */
-    int BM, BN, sp;
-    wgrad_fast_cfg(a, M, C, Kdim, KH * KW, &BM, &BN, &sp);
-    slabs = (size_t)sp * M * Np * sizeof(float);
-    int BM2, BN2;
-    wgrad_tile(M, &BM2, &BN2);
-    const int s2 = wgrad_splits(M, Np, Kdim, BM2, BN2);
-    const size_t alt = s2 > 1 ? (size_t)s2 * M * Np * sizeof(float) : 0;
-    if (alt > slabs) slabs = alt;
-  } else {
-    int BM, BN;
-    wgrad_tile(M, &BM, &BN);
-    const int s = wgrad_splits(M, Np, Kdim, BM, BN);
-    slabs = s > 1 ? (size_t)s * M * Np * sizeof(float) : 0;
+// classes of the two tiny-M VALU families (small has no geometry part; small-window shares wgrad_same_geom with head / stem)
+static bool small_win_class(int M, int KH, int KW) { return M <= 4 && KH == KW && (KH == 3 || KH == 5 || KH == 7); }
+static bool small_class(int M, int KH, int KW) { return M <= 4 && KH == KW && (KH == 7 || KH == 4 || KH == 3); }
+static bool wgrad_same_geom(const WGradShape& s) {   // "same" odd kernel, stride 1
+  return s.stride == 1 && s.pad == s.KH / 2 && s.OH == s.H && s.OW == s.W && s.H > s.pad && s.W > s.pad;
+}
+static size_t round256(size_t n) { return (n + 255) / 256 * 256; }
+
+// allow_wino: the caller's workspace reserves the F(2x2) transforms (not the one-hot dense slice, not the transposed conv)
+static WGradPlan plan_wgrad(const HimAlgo& a, const WGradShape& s, bool allow_wino) {
+  WGradPlan p;
+  memset(&p, 0, sizeof(p));
+  p.algo = a;
+  p.s = s;
+  p.splits = 1;
+  p.reduce = true;
+  const int M = s.M, C = s.C, Kdim = s.Kdim();
+  const auto slabs = [&](int n) { return (size_t)n * M * s.Np() * sizeof(float); };
+  const bool head_c = fewch_class(a, M, C, s.KH, s.KW), stem_c = fewch_class(a, C, M, s.KH, s.KW);
+  const bool win_c = small_win_class(M, s.KH, s.KW), small_c = small_class(M, s.KH, s.KW), fast_c = wgrad_fast_class(a, M, C);
+  const int fewch_tc = head_c ? C : M, slices = small_wgrad_slices(C, Kdim), tiny_n = std::max(slices, SMALL_WIN_SLOTS);
+  int gBM, gBN, fBM = 0, fBN = 0, fs = 0;
+  wgrad_tile(M, &gBM, &gBN);
+  int gs = wgrad_splits(M, s.Np(), Kdim, gBM, gBN);
+  // a tiny-M 5x5 off the small-window family lands on the generic kernel, but its class reserves the tiny families' slabs
+  // only: no more splits than those (more -- up to 512, from 65 792 positions on -- were refused at the reported size)
+  if (win_c && !small_c && !head_c) gs = std::min(gs, tiny_n);
+  if (fast_c) wgrad_fast_cfg(a, M, C, Kdim, s.KH * s.KW, &fBM, &fBN, &fs);
+  const size_t generic = gs > 1 ? slabs(gs) : 0, tiny = slabs(tiny_n);
+  // the fast kernel reads both operands through buffer resources (31-bit byte offsets)
+  const bool fits31 = (unsigned long long)s.B * M * s.OH * s.OW * 4ull < (1ull << 31) &&
+                      (unsigned long long)s.B * C * s.H * s.W * 4ull < (1ull << 31);
+  if (allow_wino && wino_wgrad_ok(a, M, C, s.KH, s.KW, s.stride, s.pad, s.H, s.W) && s.OH == s.H && s.OW == s.W) {
+    p.family = WGRAD_WINO;   // its region is exact, not a class bound: every term of the predicate is in the descriptor
+    p.need_bytes = wino_wgrad_floats(s.B, M, C, s.OH, s.OW) * sizeof(float);
+    p.slab_bytes = round256(p.need_bytes);
+    return p;
   }
-  return ((slabs + 255) / 256) * 256;
-}
-static size_t wgrad_ws_bytes(const HimAlgo& a, int M, int C, int KH, int KW, int Kdim, int biasC, size_t wino_floats = 0) {
-  return wgrad_slab_bytes(a, M, C, KH, KW, Kdim, wino_floats) + bias_ws_bytes(biasC);
-}
-static size_t conv_wino_wgrad_floats(const HimConv2d* d) {
-  return wino_wgrad_ok(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad, d->H, d->W)
-             ? wino_wgrad_floats(d->B, d->Cout, d->Cin, d->OH, d->OW)
-             : 0;
+  if ((head_c || stem_c) && wgrad_same_geom(s)) {
+    p.family = head_c ? WGRAD_HEAD : WGRAD_STEM;
+    p.splits = std::min(fewch_geom(head_c, s.B, s.H, s.W, s.pad).ntask, FEWCH_WGS);
+    p.need_bytes = fewch_need_bytes(fewch_tc, s.KH, p.splits);
+  } else if (win_c && !algo_off(a, HIM_ALGO_NO_SMALL_WIN) && wgrad_same_geom(s)) {
+    p.family = WGRAD_SMALL_WIN;   // tasks = images x 64-column strips x 64-row chunks (run_wgrad)
+    p.splits = std::min(s.B * cdiv(s.W, 64) * cdiv(s.H, 64), SMALL_WIN_SLOTS);
+    p.need_bytes = slabs(p.splits);
+  } else if (small_c) {
+    p.family = WGRAD_SMALL;
+    p.splits = slices;
+    p.kchunk = cdiv(Kdim, slices);
+    p.need_bytes = slabs(slices);
+  } else if (fast_c && s.OH * s.OW >= 4 && fits31) {
+    p.family = WGRAD_FAST;
+    p.BM = fBM, p.BN = fBN, p.splits = fs;
+    p.kchunk = (cdiv(Kdim, fs) + 31) / 32 * 32;
+    p.need_bytes = slabs(fs);
+  } else {
+    p.family = WGRAD_GENERIC;
+    p.BM = gBM, p.BN = gBN, p.splits = gs;
+    p.kchunk = (cdiv(Kdim, gs) + 31) / 32 * 32;
+    p.reduce = gs > 1;
+    p.need_bytes = generic;
+  }
+  // The slab region: the largest need among the families the CLASS admits.  Kept worst cases that no plan reaches: all
+  // FEWCH_WGS workgroups for head / stem; for the tiny-M classes both the small family's slices and all SMALL_WIN_SLOTS,
+  // whichever of the two classes holds and whether or not the small-window family is switched off.
+  size_t b;
+  if (head_c || stem_c) b = std::max(std::max(fewch_need_bytes(fewch_tc, s.KH, FEWCH_WGS), generic), (win_c || small_c) ? tiny : 0);
+  else if (win_c || small_c) b = tiny;
+  else if (fast_c) b = std::max(slabs(fs), generic);
+  else b = generic;
+  p.slab_bytes = round256(b);
+  return p;
 }
 
-// generic weight gradient: dW[M][C*KH*KW] from dy[B][M][OH][OW] and x[B][C][H][W]
-static int run_wgrad(const HimAlgo& a, const float* dy, const float* x, float* dw, int M, int C, int B, int H, int W, int OH,
-                     int OW, int KH, int KW, int stride, int pad, int pad_mode, int accumulate, void* ws,
-                     size_t ws_bytes, hipStream_t st, const float* kept_v = nullptr) {
+// the tail of every slab family: the launch's status, then the fixed-order sum of the partials into dw
+static int wgrad_finish(const WGradPlan& p, const char* what, const float* part, float* dw, int accumulate, hipStream_t st) {
+  const int rc = check_launch(what);
+  if (rc || !p.reduce) return rc;
+  if (p.family == WGRAD_FAST) {
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(p.s.C / 64, p.s.M), dim3(256), 0, st, part, dw, p.s.M, p.s.C, p.s.KH * p.s.KW,
+                       p.splits, accumulate);
+    return check_launch("wgrad_finish");
+  }
+  const long long n = (long long)p.s.M * p.s.Np();
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(std::min<long long>(cdiv(n, 256), 4096)), dim3(256), 0, st, part, dw, n, p.splits,
+                     accumulate);
+  return check_launch("slab_reduce");
+}
+
+// kept_v: the forward's transformed input in place of x -- which kernels run INSIDE the Winograd family, not which family
+static int run_wgrad(const WGradPlan& pl, const float* dy, const float* x, float* dw, int accumulate, void* ws, size_t ws_bytes,
+                     hipStream_t st, const float* kept_v = nullptr) {
+  if (pl.need_bytes && (ws_bytes < pl.need_bytes || !ws))
+    return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", pl.need_bytes, ws_bytes);
+  const WGradShape& s = pl.s;
+  const int M = s.M, C = s.C, B = s.B, H = s.H, W = s.W, KH = s.KH;
+  const bool refl = s.pad_mode == HIM_PAD_REFLECT;
   WGradP p;
   p.dy = dy;
   p.x = x;
-  p.M = M;
-  p.C = C;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.OH = OH;
-  p.OW = OW;
-  p.KH = KH;
-  p.KW = KW;
-  p.stride = stride;
-  p.pad = pad;
-  p.pad_mode = pad_mode;
-  p.Np = C * KH * KW;
-  p.Kdim = B * OH * OW;
-  p.fKK = make_fastdiv((uint32_t)(KH * KW));
-  p.fKW = make_fastdiv((uint32_t)KW);
-  p.fOW = make_fastdiv((uint32_t)OW);
-  if (wino_wgrad_ok(a, M, C, KH, KW, stride, pad, H, W) && OH == H && OW == W) {
-    // dU = dM x V^T per Winograd position (batched NT GEMM), then dw (+)= G^T dU G
-    const size_t need = wino_wgrad_floats(B, M, C, OH, OW) * sizeof(float);
-    if (ws_bytes < need || !ws) return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", need, ws_bytes);
-    const WinoGeom gx = wino_geom(B, C, H, W, OH, OW, 1);
-    WinoGeom gd = gx;
-    gd.C = M;
-    float* Vt = (float*)ws;                          // [16][Tp][C]
-    float* dM = Vt + (size_t)16 * C * gx.Tp;         // [16][M][Tp]
-    float* dU = dM + (size_t)16 * M * gx.Tp;         // [16][M][C]
-    const int tb = wino_tblock(a);
-    int rcw;
-    if (kept_v) {
-      // the forward's transformed input V[16][C][Tp] IS the column operand (tiles = the reduction index, contiguous):
-      // no transposed input transform, both GEMM operands K-contiguous (him_bgemm.inc, layouts (0, 0))
-      hipLaunchKernelGGL(wino_dy_kernel, dim3(cdiv(gx.Tp, tb), M), dim3(tb), 0, st, dy, dM, gd);
-      rcw = check_launch("wino_dy");
+  p.out = pl.reduce ? (float*)ws : dw;
+  p.M = M, p.C = C, p.B = B, p.H = H, p.W = W, p.OH = s.OH, p.OW = s.OW;
+  p.KH = KH, p.KW = s.KW, p.stride = s.stride, p.pad = s.pad, p.pad_mode = s.pad_mode;
+  p.Np = s.Np(), p.Kdim = s.Kdim(), p.kchunk = pl.kchunk, p.splits = pl.splits;
+  p.accumulate = pl.family == WGRAD_GENERIC ? accumulate : 0;
+  p.fKK = make_fastdiv((uint32_t)(KH * s.KW));
+  p.fKW = make_fastdiv((uint32_t)s.KW);
+  p.fOW = make_fastdiv((uint32_t)s.OW);
+  const dim3 block(256);
+  switch (pl.family) {
+    case WGRAD_WINO: {
+      // dU = dM x V^T per Winograd position (batched NT GEMM), then dw (+)= G^T dU G
+      const WinoGeom gx = wino_geom(B, C, H, W, s.OH, s.OW, 1);
+      WinoGeom gd = gx;
+      gd.C = M;
+      float* Vt = (float*)ws;                          // [16][Tp][C]
+      float* dM = Vt + (size_t)16 * C * gx.Tp;         // [16][M][Tp]
+      float* dU = dM + (size_t)16 * M * gx.Tp;         // [16][M][C]
+      const int tb = wino_tblock(pl.algo);
+      int rcw;
+      if (kept_v) {
+        // the forward's transformed input V[16][C][Tp] IS the column operand (tiles = the reduction index, contiguous):
+        // no transposed input transform, both GEMM operands K-contiguous (him_bgemm.inc, layouts (0, 0))
+        hipLaunchKernelGGL(wino_dy_kernel, dim3(cdiv(gx.Tp, tb), M), dim3(tb), 0, st, dy, dM, gd);
+        rcw = check_launch("wino_dy");
+        if (rcw) return rcw;
+        rcw = launch_bgemm(dM, kept_v, dU, M, gx.Tp, C, 16, 4, 0, 0, false, st);
+      } else {
+        const dim3 gin(cdiv(C, tb), gx.Tp);
+        if (refl) hipLaunchKernelGGL((wino_input_t_kernel<true>), gin, dim3(tb), 0, st, x, Vt, gx);
+        else hipLaunchKernelGGL((wino_input_t_kernel<false>), gin, dim3(tb), 0, st, x, Vt, gx);
+        hipLaunchKernelGGL(wino_dy_kernel, dim3(cdiv(gx.Tp, tb), M), dim3(tb), 0, st, dy, dM, gd);
+        rcw = check_launch("wino_wgrad_transforms");
+        if (rcw) return rcw;
+        rcw = wino_batched_gemm(pl.algo, dM, Vt, dU, M, gx.Tp, C, st);
+      }
       if (rcw) return rcw;
-      rcw = launch_bgemm(dM, kept_v, dU, M, gx.Tp, C, 16, 4, 0, 0, false, st);
-    } else {
-      const dim3 gin(cdiv(C, tb), gx.Tp);
-      if (pad_mode == HIM_PAD_REFLECT) hipLaunchKernelGGL((wino_input_t_kernel<true>), gin, dim3(tb), 0, st, x, Vt, gx);
-      else hipLaunchKernelGGL((wino_input_t_kernel<false>), gin, dim3(tb), 0, st, x, Vt, gx);
-      hipLaunchKernelGGL(wino_dy_kernel, dim3(cdiv(gx.Tp, tb), M), dim3(tb), 0, st, dy, dM, gd);
-      rcw = check_launch("wino_wgrad_transforms");
-      if (rcw) return rcw;
-      rcw = wino_batched_gemm(a, dM, Vt, dU, M, gx.Tp, C, st);
+      hipLaunchKernelGGL(wino_wgrad_out_kernel, dim3(cdiv(C, 256), M), dim3(256), 0, st, (const float*)dU, dw, M, C,
+                         accumulate);
+      return check_launch("wino_wgrad_out");
     }
-    if (rcw) return rcw;
-    hipLaunchKernelGGL(wino_wgrad_out_kernel, dim3(cdiv(C, 256), M), dim3(256), 0, st, (const float*)dU, dw, M, C,
-                       accumulate);
-    return check_launch("wino_wgrad_out");
-  }
-  if (fewch_head_ok(a, M, C, KH, KW, stride, pad, H, W, OH, OW))
-    return run_wgrad_fewch(a, true, dy, x, dw, M, C, B, H, W, KH, pad, pad_mode, accumulate, ws, ws_bytes, st);
-  if (fewch_stem_ok(a, M, C, KH, KW, stride, pad, H, W, OH, OW))
-    return run_wgrad_fewch(a, false, dy, x, dw, M, C, B, H, W, KH, pad, pad_mode, accumulate, ws, ws_bytes, st);
-  if (small_win_ok(a, M, KH, KW, stride, pad, H, W, OH, OW)) {
-    const int nsx = cdiv(W, 64), rows_per = 64, nyc = cdiv(H, rows_per), ntasks = B * nsx * nyc;
-    const int slots = std::min(ntasks, SMALL_WIN_SLOTS);
-    const size_t need = (size_t)slots * M * p.Np * sizeof(float);
-    if (ws_bytes < need || !ws) return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", need, ws_bytes);
-    p.out = (float*)ws;
-    const dim3 grid(slots, cdiv(C, 4)), block(256);
-    const bool refl = pad_mode == HIM_PAD_REFLECT;
+    case WGRAD_HEAD:
+    case WGRAD_STEM:
+      return run_wgrad_fewch(pl.family == WGRAD_HEAD, dy, x, dw, M, C, B, H, W, KH, s.pad, s.pad_mode, pl.splits, accumulate, ws, st);
+    case WGRAD_SMALL_WIN: {
+      const int nsx = cdiv(W, 64), rows_per = 64, nyc = cdiv(H, rows_per), ntasks = B * nsx * nyc;
+      const dim3 grid(pl.splits, cdiv(C, 4));
 #define HIM_SWK(MMv, KSv)                                                                                         \
   if (M == MMv && KH == KSv) {                                                                                    \
     constexpr int TRv = (MMv * KSv * KSv > 90) ? (KSv + 1) / 2 : KSv;  /* band split once the accumulators pass ~90 */ \
@@ -636,61 +693,30 @@ static int run_wgrad(const HimAlgo& a, const float* dy, const float* x, float* d
     if (refl) hipLaunchKernelGGL((wgrad_small_win_kernel<MMv, KSv, TRv, true>), gridz, block, 0, st, p, nsx, nyc, rows_per, ntasks); \
     else hipLaunchKernelGGL((wgrad_small_win_kernel<MMv, KSv, TRv, false>), gridz, block, 0, st, p, nsx, nyc, rows_per, ntasks);     \
   }
-    HIM_SWK(1, 3) HIM_SWK(2, 3) HIM_SWK(3, 3) HIM_SWK(4, 3)
-    HIM_SWK(1, 5) HIM_SWK(2, 5) HIM_SWK(3, 5) HIM_SWK(4, 5)
-    HIM_SWK(1, 7) HIM_SWK(2, 7) HIM_SWK(3, 7) HIM_SWK(4, 7)
+      HIM_SWK(1, 3) HIM_SWK(2, 3) HIM_SWK(3, 3) HIM_SWK(4, 3)
+      HIM_SWK(1, 5) HIM_SWK(2, 5) HIM_SWK(3, 5) HIM_SWK(4, 5)
+      HIM_SWK(1, 7) HIM_SWK(2, 7) HIM_SWK(3, 7) HIM_SWK(4, 7)
 #undef HIM_SWK
-    int rc0 = check_launch("wgrad_small_win");
-    if (rc0) return rc0;
-    const long long n = (long long)M * p.Np;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(std::min<long long>(cdiv(n, 256), 4096)), dim3(256), 0, st,
-                       (const float*)ws, dw, n, slots, accumulate);
-    return check_launch("slab_reduce");
-  }
-  if (small_wgrad_ok(M, KH, KW)) {
-    const int slices = small_wgrad_slices(C, p.Kdim);
-    const size_t need = (size_t)slices * M * p.Np * sizeof(float);
-    if (ws_bytes < need || !ws) return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", need, ws_bytes);
-    p.splits = slices;
-    p.accumulate = 0;
-    p.kchunk = cdiv(p.Kdim, slices);
-    p.out = (float*)ws;
-    dim3 grid(C, slices), block(256);
-    const bool refl = pad_mode == HIM_PAD_REFLECT;
+      return wgrad_finish(pl, "wgrad_small_win", (const float*)ws, dw, accumulate, st);
+    }
+    case WGRAD_SMALL: {
+      const dim3 grid(C, pl.splits);
 #define HIM_WS(MMv, TJv)                                                                             \
   if (M == MMv && KH == TJv) {                                                                       \
     if (refl) hipLaunchKernelGGL((wgrad_small_kernel<MMv, TJv, true>), grid, block, 0, st, p);        \
     else hipLaunchKernelGGL((wgrad_small_kernel<MMv, TJv, false>), grid, block, 0, st, p);            \
   }
-    HIM_WS(1, 7) HIM_WS(2, 7) HIM_WS(3, 7) HIM_WS(4, 7)
-    HIM_WS(1, 4) HIM_WS(2, 4) HIM_WS(3, 4) HIM_WS(4, 4)
-    HIM_WS(1, 3) HIM_WS(2, 3) HIM_WS(3, 3) HIM_WS(4, 3)
+      HIM_WS(1, 7) HIM_WS(2, 7) HIM_WS(3, 7) HIM_WS(4, 7)
+      HIM_WS(1, 4) HIM_WS(2, 4) HIM_WS(3, 4) HIM_WS(4, 4)
+      HIM_WS(1, 3) HIM_WS(2, 3) HIM_WS(3, 3) HIM_WS(4, 3)
 #undef HIM_WS
-    int rc0 = check_launch("wgrad_small");
-    if (rc0) return rc0;
-    const long long n = (long long)M * p.Np;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(std::min<long long>(cdiv(n, 256), 4096)), dim3(256), 0, st,
-                       (const float*)ws, dw, n, slices, accumulate);
-    return check_launch("slab_reduce");
-  }
-  // the fast kernel reads both operands through buffer resources (31-bit byte offsets)
-  const bool fits31 = (unsigned long long)B * M * OH * OW * 4ull < (1ull << 31) &&
-                      (unsigned long long)B * C * H * W * 4ull < (1ull << 31);
-  if (wgrad_fast_ok(a, M, C, OH, OW) && fits31) {
-    int fBM, fBN, fs;
-    wgrad_fast_cfg(a, M, C, p.Kdim, KH * KW, &fBM, &fBN, &fs);
-    const size_t need = (size_t)fs * M * p.Np * sizeof(float);
-    if (ws_bytes < need || !ws) return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", need, ws_bytes);
-    p.splits = fs;
-    p.accumulate = 0;
-    int kc = cdiv(p.Kdim, fs);
-    p.kchunk = ((kc + 31) / 32) * 32;
-    p.out = (float*)ws;
-    dim3 grid(p.Np / fBN, cdiv(M, fBM), fs), block(256);
-    const bool refl = pad_mode == HIM_PAD_REFLECT;
+      return wgrad_finish(pl, "wgrad_small", (const float*)ws, dw, accumulate, st);
+    }
+    case WGRAD_FAST: {
+      const dim3 grid(p.Np / pl.BN, cdiv(M, pl.BM), pl.splits);
 #define HIM_WF(TMv, TNv)                                                                              \
   {                                                                                                   \
-    if ((OH * OW) % 4 == 0) {                                                                         \
+    if ((s.OH * s.OW) % 4 == 0) {                                                                     \
       if (refl) hipLaunchKernelGGL((wgrad_fast_kernel<TMv, TNv, true, true>), grid, block, 0, st, p);  \
       else hipLaunchKernelGGL((wgrad_fast_kernel<TMv, TNv, false, true>), grid, block, 0, st, p);      \
     } else {                                                                                          \
@@ -698,53 +724,29 @@ static int run_wgrad(const HimAlgo& a, const float* dy, const float* x, float* d
       else hipLaunchKernelGGL((wgrad_fast_kernel<TMv, TNv, false, false>), grid, block, 0, st, p);     \
     }                                                                                                 \
   }
-    if (fBM == 128 && fBN == 128) HIM_WF(2, 2)
-    else if (fBM == 128) HIM_WF(2, 1)
-    else if (fBN == 128) HIM_WF(1, 2)
-    else HIM_WF(1, 1)
+      if (pl.BM == 128 && pl.BN == 128) HIM_WF(2, 2)
+      else if (pl.BM == 128) HIM_WF(2, 1)
+      else if (pl.BN == 128) HIM_WF(1, 2)
+      else HIM_WF(1, 1)
 #undef HIM_WF
-    int rc0 = check_launch("wgrad_fast");
-    if (rc0) return rc0;
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(C / 64, M), dim3(256), 0, st, (const float*)ws, dw, M, C, KH * KW, fs,
-                       accumulate);
-    return check_launch("wgrad_finish");
+      return wgrad_finish(pl, "wgrad_fast", (const float*)ws, dw, accumulate, st);
+    }
+    case WGRAD_GENERIC: {
+      const dim3 grid(cdiv(p.Np, pl.BN), cdiv(M, pl.BM), pl.splits);
+      if (pl.BM == 128) {
+        if (refl) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2, false>), grid, block, 0, st, p);
+      } else if (pl.BM == 64) {
+        if (refl) hipLaunchKernelGGL((wgrad_kernel<1, 4, 2, 1, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((wgrad_kernel<1, 4, 2, 1, false>), grid, block, 0, st, p);
+      } else {
+        if (refl) hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1, false>), grid, block, 0, st, p);
+      }
+      return wgrad_finish(pl, "wgrad", (const float*)ws, dw, accumulate, st);
+    }
   }
-  int BM, BN;
-  wgrad_tile(M, &BM, &BN);
-  const int splits = wgrad_splits(M, p.Np, p.Kdim, BM, BN);
-  p.splits = splits;
-  p.accumulate = accumulate;
-  int kchunk = cdiv(p.Kdim, splits);
-  kchunk = ((kchunk + 31) / 32) * 32;
-  p.kchunk = kchunk;
-  if (splits > 1) {
-    const size_t need = (size_t)splits * M * p.Np * sizeof(float);
-    if (ws_bytes < need || !ws) return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", need, ws_bytes);
-    p.out = (float*)ws;
-  } else {
-    p.out = dw;
-  }
-  dim3 grid(cdiv(p.Np, BN), cdiv(M, BM), splits), block(256);
-  const bool refl = pad_mode == HIM_PAD_REFLECT;
-  if (BM == 128) {
-    if (refl) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2, false>), grid, block, 0, st, p);
-  } else if (BM == 64) {
-    if (refl) hipLaunchKernelGGL((wgrad_kernel<1, 4, 2, 1, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((wgrad_kernel<1, 4, 2, 1, false>), grid, block, 0, st, p);
-  } else {
-    if (refl) hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1, false>), grid, block, 0, st, p);
-  }
-  int rc = check_launch("wgrad");
-  if (rc) return rc;
-  if (splits > 1) {
-    const long long n = (long long)M * p.Np;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(std::min<long long>(cdiv(n, 256), 4096)), dim3(256), 0, st,
-                       (const float*)ws, dw, n, splits, accumulate);
-    rc = check_launch("slab_reduce");
-  }
-  return rc;
+  return fail(HIM_E_INVALID, "wgrad: no family");
 }
 
 static int run_bias_grad(const float* dy, float* db, int B, int C, int hw, int accumulate, void* ws, size_t ws_bytes,
@@ -1509,14 +1511,13 @@ int him_conv2d_fwd_panel_keep(const HimConv2d* d, const float* x, const void* pa
 // dw from x -- or from the forward's kept transform of it -- then dbias behind the slab region
 static int conv_bwd_weight(const HimConv2d* d, const float* x, const float* keep, const float* dy, float* dw, float* dbias,
                            int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
+  const WGradPlan p = plan_wgrad(d->algo, wgrad_shape(d), true);
   if (dw) {
-    int rc = run_wgrad(d->algo, dy, x, dw, d->Cout, d->Cin, d->B, d->H, d->W, d->OH, d->OW, d->KH, d->KW, d->stride, d->pad,
-                       d->pad_mode, accumulate, ws, ws_bytes, st, keep);
+    int rc = run_wgrad(p, dy, x, dw, accumulate, ws, ws_bytes, st, keep);
     if (rc) return rc;
   }
   if (!dbias) return HIM_OK;
-  const size_t off = wgrad_slab_bytes(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->B * d->OH * d->OW, conv_wino_wgrad_floats(d));
-  return run_bias_grad_behind(dy, dbias, d->B, d->Cout, d->OH * d->OW, accumulate, ws, ws_bytes, off, st);
+  return run_bias_grad_behind(dy, dbias, d->B, d->Cout, d->OH * d->OW, accumulate, ws, ws_bytes, p.slab_bytes, st);
 }
 int him_conv2d_bwd_weight_kept(const HimConv2d* d, const float* keep, const float* dy, float* dw, float* dbias, int accumulate,
                                void* ws, size_t ws_bytes, void* stream) {
@@ -1527,7 +1528,20 @@ int him_conv2d_bwd_weight_kept(const HimConv2d* d, const float* keep, const floa
 }
 
 size_t him_conv2d_bwd_weight_ws(const HimConv2d* d) {
-  return d ? wgrad_ws_bytes(d->algo, d->Cout, d->Cin, d->KH, d->KW, d->B * d->OH * d->OW, d->Cout, conv_wino_wgrad_floats(d)) : 0;
+  return d ? plan_wgrad(d->algo, wgrad_shape(d), true).slab_bytes + bias_ws_bytes(d->Cout) : 0;
+}
+// diagnostics (include/him.h): the plan the weight gradient of a descriptor runs
+static int report_wgrad_plan(const WGradPlan& p, int* family, size_t* need_bytes, int* splits, int* tile_m, int* tile_n) {
+  if (family) *family = p.family;
+  if (need_bytes) *need_bytes = p.need_bytes;
+  if (splits) *splits = p.splits;
+  if (tile_m) *tile_m = p.BM;
+  if (tile_n) *tile_n = p.BN;
+  return HIM_OK;
+}
+int him_conv2d_bwd_weight_plan(const HimConv2d* d, int* family, size_t* need_bytes, int* splits, int* tile_m, int* tile_n) {
+  const int rc = check_conv(d);
+  return rc ? rc : report_wgrad_plan(plan_wgrad(d->algo, wgrad_shape(d), true), family, need_bytes, splits, tile_m, tile_n);
 }
 
 int him_conv2d_bwd_weight(const HimConv2d* d, const float* x, const float* dy, float* dw, float* dbias,
@@ -1680,8 +1694,8 @@ static int onehot_bwd_weight_impl(const HimConv2d* d, const float* label, int n_
         rc = him_copy_channels(x, d->Cin, NC, xd, Cd, 0, Cd, d->B, HW, nullptr, 0, 0, stream);
         if (rc) return rc;
       }
-      rc = run_wgrad(d->algo, dy, x_dense ? x : xd, dwd, d->Cout, Cd, d->B, d->H, d->W, d->OH, d->OW, d->KH, d->KW, d->stride, d->pad,
-                     d->pad_mode, 0, wws, wgrad_slab_bytes(d->algo, d->Cout, Cd, d->KH, d->KW, d->B * d->OH * d->OW), st);
+      const WGradPlan pd = onehot_dense_wgrad_plan(d, NC);
+      rc = run_wgrad(pd, dy, x_dense ? x : xd, dwd, 0, wws, pd.slab_bytes, st);
       if (rc) return rc;
       hipLaunchKernelGGL(onehot_dense_w_kernel, dim3(cdiv((long long)d->Cout * Cd * KK, 256)), dim3(256), 0, st, dw, dwd,
                          d->Cout, d->Cin, NC, KK, 1, accumulate);
@@ -1783,7 +1797,12 @@ int him_deconv2d_bwd_data_panel(const HimDeconv2d* t, const float* dy, const voi
 size_t him_deconv2d_bwd_weight_ws(const HimDeconv2d* t) {
   HimConv2d c;
   if (adjoint_of(t, &c)) return 0;
-  return wgrad_ws_bytes(c.algo, c.Cout, c.Cin, c.KH, c.KW, c.B * c.OH * c.OW, t->Cout);
+  return plan_wgrad(c.algo, wgrad_shape(&c), false).slab_bytes + bias_ws_bytes(t->Cout);
+}
+int him_deconv2d_bwd_weight_plan(const HimDeconv2d* t, int* family, size_t* need_bytes, int* splits, int* tile_m, int* tile_n) {
+  HimConv2d c;
+  const int rc = adjoint_of(t, &c);
+  return rc ? rc : report_wgrad_plan(plan_wgrad(c.algo, wgrad_shape(&c), false), family, need_bytes, splits, tile_m, tile_n);
 }
 
 int him_deconv2d_bwd_weight(const HimDeconv2d* t, const float* x, const float* dy, float* dw, float* dbias,
@@ -1791,15 +1810,14 @@ int him_deconv2d_bwd_weight(const HimDeconv2d* t, const float* x, const float* d
   HimConv2d c;
   int rc = adjoint_of(t, &c);
   if (rc) return rc;
-  // adjoint conv: "input" = deconv output gradient dy, "output gradient" = deconv input x
+  // adjoint conv: "input" = deconv output gradient dy, "output gradient" = deconv input x; no Winograd space reserved
+  const WGradPlan p = plan_wgrad(c.algo, wgrad_shape(&c), false);
   if (dw) {
-    rc = run_wgrad(c.algo, x, dy, dw, c.Cout, c.Cin, c.B, c.H, c.W, c.OH, c.OW, c.KH, c.KW, c.stride, c.pad, HIM_PAD_ZERO,
-                   accumulate, ws, ws_bytes, (hipStream_t)stream);
+    rc = run_wgrad(p, x, dy, dw, accumulate, ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
   }
   if (!dbias) return HIM_OK;
-  return run_bias_grad_behind(dy, dbias, t->B, t->Cout, t->OH * t->OW, accumulate, ws, ws_bytes,
-                              wgrad_slab_bytes(c.algo, c.Cout, c.Cin, c.KH, c.KW, c.B * c.OH * c.OW), (hipStream_t)stream);
+  return run_bias_grad_behind(dy, dbias, t->B, t->Cout, t->OH * t->OW, accumulate, ws, ws_bytes, p.slab_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -334,12 +334,17 @@ static size_t onehot_fwd_ws_bytes(const HimConv2d* d, int NC) {
   }
   return n * sizeof(float) + 256;
 }
+// the dense channels' slice of the weight gradient: its workspace reserves no Winograd transforms
+static WGradPlan onehot_dense_wgrad_plan(const HimConv2d* d, int NC) {
+  const HimConv2d dd = onehot_dense_desc(d, NC);
+  return plan_wgrad(d->algo, wgrad_shape(&dd), false);
+}
 static size_t onehot_wgrad_ws_bytes(const HimConv2d* d, int NC) {
   const int Cd = d->Cin - NC, KK = d->KH * d->KW;
   size_t n = (size_t)onehot_wgrad_blocks(d) * KK * NC * d->Cout + 64;
   if (Cd > 0) {
     n += ((size_t)d->B * Cd * d->H * d->W + 63) / 64 * 64 + ((size_t)d->Cout * Cd * KK + 63) / 64 * 64;
-    return n * sizeof(float) + wgrad_slab_bytes(d->algo, d->Cout, Cd, d->KH, d->KW, d->B * d->OH * d->OW) + 256;
+    return n * sizeof(float) + onehot_dense_wgrad_plan(d, NC).slab_bytes + 256;
   }
   return n * sizeof(float) + 256;
 }

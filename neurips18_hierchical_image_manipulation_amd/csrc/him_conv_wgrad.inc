@@ -417,9 +417,9 @@ __global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restri
   for (int i = threadIdx.x; i < nel; i += 256) dst[i] = accumulate ? dst[i] + sm[i] : sm[i];
 }
 
-static bool wgrad_fast_ok(const HimAlgo& a, int M, int C, int OH, int OW) {
-  return !algo_off(a, HIM_ALGO_GENERIC_CONV) && M > 4 && (C % 64) == 0 && OH * OW >= 4;   // planes with OH*OW % 4 != 0: scalar dY loads
-}
+// the class (channels) of the fast family; its geometry part -- OH*OW >= 4 (planes with OH*OW % 4 != 0: scalar dY loads) and
+// both tensors under 2 GiB (31-bit buffer offsets) -- is plan_wgrad's (him_conv.hip)
+static bool wgrad_fast_class(const HimAlgo& a, int M, int C) { return !algo_off(a, HIM_ALGO_GENERIC_CONV) && M > 4 && (C % 64) == 0; }
 static void wgrad_fast_cfg(const HimAlgo& a, int M, int C, int Kdim, int KK, int* BM, int* BN, int* splits) {
   // (64-row / 64-column tiles where 128 fit: no change of the step, round 3 -- unlike the conv kernel's tile)
   *BM = (M > 64 && a.wgrad_tile == 0) ? 128 : 64;

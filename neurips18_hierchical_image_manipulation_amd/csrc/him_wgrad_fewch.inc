@@ -199,34 +199,26 @@ __global__ __launch_bounds__(256) void wgrad_fewch_finish_kernel(const float* __
 
 static const int FEWCH_WGS = 256;
 static bool fewch_off(const HimAlgo& a) { return algo_off(a, HIM_ALGO_NO_FEWCH_MFMA); }
-// head: M <= 4 outputs, C % 32 == 0 wide inputs; stem: C <= 4 inputs, M % 32 == 0 outputs
-static bool fewch_head_ok(const HimAlgo& a, int M, int C, int KH, int KW, int stride, int pad, int H, int W, int OH, int OW) {
-  return !fewch_off(a) && M <= 4 && C >= 32 && (C % 32) == 0 && KH == KW && (KH == 5 || KH == 7) && stride == 1 &&
-         pad == KH / 2 && OH == H && OW == W && H > pad && W > pad;
-}
-static bool fewch_stem_ok(const HimAlgo& a, int M, int C, int KH, int KW, int stride, int pad, int H, int W, int OH, int OW) {
-  return !fewch_off(a) && C <= 4 && M >= 32 && (M % 32) == 0 && KH == KW && (KH == 5 || KH == 7) && stride == 1 &&
-         pad == KH / 2 && OH == H && OW == W && H > pad && W > pad;
+// The class (channels and kernel) of the few-channel families: `narrow` <= 4 channels on one side, `wide` % 32 == 0 on the
+// other.  head: (M, C) = (narrow, wide); stem: (C, M).  The geometry part is wgrad_same_geom (him_conv.hip plan_wgrad).
+static bool fewch_class(const HimAlgo& a, int narrow, int wide, int KH, int KW) {
+  return !fewch_off(a) && narrow <= 4 && wide >= 32 && (wide % 32) == 0 && KH == KW && (KH == 5 || KH == 7);
 }
 static int fewch_groups(int TC, int* CT) {
   *CT = (TC % 64) == 0 ? 2 : 1;
   return TC / (32 * *CT);
 }
-static size_t fewch_ws_floats(int TC, int KS) {
+// bytes of the `wgs` workgroups' partial tiles
+static size_t fewch_need_bytes(int TC, int KS, int wgs) {
   int CT;
   const int grp = fewch_groups(TC, &CT);
-  return (size_t)grp * FEWCH_WGS * KS * CT * 1024;
+  return (size_t)grp * wgs * KS * CT * 1024 * sizeof(float);
 }
-static int run_wgrad_fewch(const HimAlgo& a, bool head, const float* dy, const float* x, float* dw, int M, int C, int B, int H, int W, int KS,
-                           int pad, int pad_mode, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
+// the walk over the wide tensor: chunks of 128 columns x row bands x images = tasks
+static FewChP fewch_geom(bool head, int B, int H, int W, int pad) {
   FewChP p;
   memset(&p, 0, sizeof(p));
-  p.T = head ? x : dy;
-  p.S = head ? dy : x;
-  p.TC = head ? C : M;
-  p.SC = head ? M : C;
   p.B = B; p.H = H; p.W = W; p.pad = pad;
-  p.reflect = pad_mode == HIM_PAD_REFLECT ? 1 : 0;
   p.head = head ? 1 : 0;
   p.TH = head ? H + 2 * pad : H;
   p.TW = head ? W + 2 * pad : W;
@@ -237,11 +229,19 @@ static int run_wgrad_fewch(const HimAlgo& a, bool head, const float* dy, const f
   p.rows_per = cdiv(p.TH, nband);
   p.nband = cdiv(p.TH, p.rows_per);
   p.ntask = B * p.nchunk * p.nband;
+  return p;
+}
+// wgs = min(tasks, FEWCH_WGS) workgroups (the plan's `splits`); ws holds fewch_need_bytes(TC, KS, wgs)
+static int run_wgrad_fewch(bool head, const float* dy, const float* x, float* dw, int M, int C, int B, int H, int W, int KS,
+                           int pad, int pad_mode, int wgs, int accumulate, void* ws, hipStream_t st) {
+  FewChP p = fewch_geom(head, B, H, W, pad);
+  p.T = head ? x : dy;
+  p.S = head ? dy : x;
+  p.TC = head ? C : M;
+  p.SC = head ? M : C;
+  p.reflect = pad_mode == HIM_PAD_REFLECT ? 1 : 0;
   int CT;
   const int grp = fewch_groups(p.TC, &CT);
-  const int wgs = std::min(p.ntask, FEWCH_WGS);
-  const size_t need = (size_t)grp * wgs * KS * CT * 1024 * sizeof(float);
-  if (ws_bytes < need || !ws) return fail(HIM_E_WORKSPACE, "wgrad needs %zu ws bytes, got %zu", need, ws_bytes);
   p.part = (float*)ws;
   const dim3 grid(wgs, grp), block(256);
 #define HIM_FEWCH(KSv, CTv)                                                                                              \

@@ -225,7 +225,7 @@ for c in ((2, 96, 37, 150, 3, 7, 1, 3, 'zero', 'none'), (2, 4, 20, 140, 32, 5, 1
         KERNEL_WHY % 'him_wgrad_fewch.inc:201')
 for c in (TAILS, PATCH, (3, 128, 8, 10, 256, 4, 1, 2, 'zero', 'none')):
     row('GENERIC_CONV %s' % 'x'.join(map(str, c[:5])), c, ALL3, dict(NOWINO, disable=A.ALGO_GENERIC_CONV), 'any', NOWINO,
-        KERNEL_WHY % 'him_conv.hip use_fast, him_conv_wgrad.inc:421')
+        KERNEL_WHY % 'him_conv.hip use_fast, him_conv_wgrad.inc:422')
 row('GENERIC_CONV deconv', DECONV, ALL3, {'disable': A.ALGO_GENERIC_CONV}, 'any', None, KERNEL_WHY % 'him_conv.hip use_fast')
 row('NO_BGEMM', wino(W512), ALL3, {'disable': A.ALGO_NO_BGEMM}, 'any', None, KERNEL_WHY % 'him_conv.hip wino_batched_gemm')
 # him_resblock.inc resblock_ok is the only reader of the bit: the layerwise path (the plain conv entry points) must not move
@@ -341,10 +341,9 @@ def test_resblock_fused_switch():
     assert lib.him_resblock_supported(ctypes.byref(d)) == 0 and lib.him_resblock_ws(ctypes.byref(d)) == 0
 
 
-@pytest.mark.parametrize('c', ONEHOT_CASES, ids=lambda c: 'x'.join(map(str, c)))
-def test_onehot_weight_gradient_per_pixel_and_per_run(c):
-    """him_conv_onehot.inc:263: NO_ONEHOT_RLE selects the per-pixel weight gradient; both forms, both accumulate modes, in
-    guarded arenas against the float64 dense convolution on the materialised one-hot tensor."""
+def onehot_both_forms(c, over):
+    """The one-hot weight gradient (and forward) of case `c` under HimAlgo `over`, per run and per pixel (NO_ONEHOT_RLE), both
+    accumulate modes, in guarded arenas of exactly the reported size against float64; returns dw per (bit, accumulate)."""
     lib = H.raw_lib()
     B, NC, Cd, Hh, W, Cout, k, pm = c
     g = torch.Generator().manual_seed(11)
@@ -357,7 +356,7 @@ def test_onehot_weight_gradient_per_pixel_and_per_run(c):
     case.w = H.rand(Cout, NC + Cd, k, k, seed=2, scale=0.05)
     got = {}
     for bit in (0, A.ALGO_NO_ONEHOT_RLE):
-        a = H.algo(disable=bit)
+        a = H.algo(**dict(over, disable=bit))
         d = case.desc(a)
         row_ = '%s|%s|onehot' % (case.tag(), H.algo_tag(a))
         nws = int(lib.him_conv2d_onehot_bwd_weight_ws(ctypes.byref(d), NC))
@@ -383,4 +382,28 @@ def test_onehot_weight_gradient_per_pixel_and_per_run(c):
                                        ar.ptr('ws'), nws, torch.cuda.current_stream().cuda_stream)
         H._finish(lib, row_ + ' fwd', rc, ar, 'cuda')
         H.check_tensor(row_ + ' fwd', 'y', 'plane', ar.t['y'].cpu(), case.ref(torch.float64, 'y'), case.ref(torch.float32, 'y'), H.DIRECT)
+    return got
+
+
+@pytest.mark.parametrize('c', ONEHOT_CASES, ids=lambda c: 'x'.join(map(str, c)))
+def test_onehot_weight_gradient_per_pixel_and_per_run(c):
+    """him_conv_onehot.inc:263: NO_ONEHOT_RLE selects the per-pixel weight gradient; both forms, both accumulate modes, in
+    guarded arenas against the float64 dense convolution on the materialised one-hot tensor."""
+    got = onehot_both_forms(c, {})
     assert not torch.equal(got[(0, 0)], got[(A.ALGO_NO_ONEHOT_RLE, 0)]), 'NO_ONEHOT_RLE did not reach the launch'
+
+
+@pytest.mark.parametrize('pm', ['reflect', 'zero'])
+def test_onehot_dense_slice_with_the_winograd_shape(pm):
+    """him_conv.hip plan_wgrad(allow_wino = false): a 3x3 "same" stem whose dense slice (128 -> 128 channels, threshold 16) has
+    the F(2x2) weight-gradient shape.  The one-hot workspace reserves no Winograd transforms; before the plan run_wgrad chose
+    Winograd all the same and the call ended in HIM_E_WORKSPACE with the label-id slice of dw already written."""
+    onehot_both_forms((1, 3, 128, 8, 8, 128, 3, pm), WINO16)
+
+
+def test_tiny_5x5_weight_gradient_fits_its_reported_workspace():
+    """him_conv.hip plan_wgrad: Cout <= 4 with a 5x5 kernel off the "same" geometry runs the generic kernel, whose splits
+    (268 here: 67 600 positions / 256) are capped at the 256 slabs its class reserves; uncapped, the call was refused."""
+    case = case_of((1, 1, 520, 520, 1, 5, 2, 2, 'zero', 'none'))
+    for acc in (0, 1):
+        run(case, {}, 'bwd_weight', accumulate=acc)
