@@ -702,6 +702,45 @@ int him_confusion(const void* pred, int pred_kind, const void* gt, int gt_kind, 
                   int W, int n, int ignore, int per_sample, int accumulate, long long* counts, int* status, void* ws,
                   size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Instance labelling of layouts (the reference ships none; its loaders expect instance maps from the dataset):
+ * connected-component labelling of a batch of class planes into instance planes in the Cityscapes convention, so that
+ * him_inst_summary, him_edges and the loader work on a layout that has no instance annotation.  Exact integer work.
+ * Per plane b of cls (B,H,W), independently of the other planes:
+ *   - a component is a maximal 4- or 8-connected set of pixels of ONE class c with thing[c] != 0;
+ *   - components of fewer than min_area pixels are no objects (min_area <= 1 keeps all);
+ *   - kept components are numbered r = 0, 1, ... in raster order of their first pixel (the smallest y * W + x);
+ *   - inst_out = base_id + r on their pixels, and the pixel's class on every other pixel (classes without instances
+ *     and dropped components).
+ *   cls:     cls_kind 0 uint8 / 1 int32 / 2 int64 / 3 fp32 holding integral values; accepted 0..255.  Never written.
+ *   thing:   256 bytes on the device, non-zero = the class has instances.
+ *   connectivity: 4 or 8.   base_id: >= 256 (1000 is the Cityscapes convention).   max_objects: 1..65536.
+ *   inst_out: (B,H,W) int32.
+ *   status:  B x 2 ints written by the device: [b][0] = number of kept components of plane b (also when it exceeds
+ *            max_objects), [b][1] = flag bits: HIM_CCL_OVERFLOW (count > max_objects, or base_id + count - 1 > 65535,
+ *            the id domain him_inst_summary accepts) | HIM_CCL_CLS_RANGE (a class is negative, > 255 or a non-integral
+ *            fp32).  With a bit set that plane's inst_out is unspecified; nothing outside inst_out, status and ws is
+ *            ever written.
+ *   ws:      him_label_instances_workspace(B, H, W) bytes (two ints per pixel and a few per tile), 16-byte aligned;
+ *            every cell that is read is written by the call first, so one workspace serves any sequence of calls on one
+ *            stream.
+ * Asynchronous, no allocation.  Seven launches on `stream`: tile pass (a 256-thread workgroup labels a tile of 32 x 64
+ * pixels by union-find on int32 parents in LDS), border pass (atomicMin on the global parents across tile borders),
+ * flatten (+ integer area counts), count / scan / rank (an exclusive prefix sum of the kept roots in raster order) and
+ * the write.  No cooperative launch, no grid-wide barrier, no workgroup waits for another.  The root of a component is
+ * its smallest pixel index whatever the order of the atomics, and ranks come from the prefix sum: inst_out and status
+ * are bit-identical from run to run.  Planes are read element by element (a lane per column), any base and any width.
+ * HIM_E_INVALID before any launch for a NULL pointer, connectivity outside {4, 8}, B, H or W < 1, H * W > 2^31 - 1,
+ * B * H * W > 2^40, base_id < 256, max_objects outside 1..65536, an unknown kind or a misaligned workspace;
+ * HIM_E_WORKSPACE for a workspace smaller than the query's size (the query returns 0 for a shape that is refused).
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_CCL_OVERFLOW 1
+#define HIM_CCL_CLS_RANGE 2
+size_t him_label_instances_workspace(int B, int H, int W);
+int him_label_instances(const void* cls, int cls_kind, int B, int H, int W, const unsigned char* thing, int connectivity,
+                        int min_area, int base_id, int max_objects, int* inst_out, int* status, void* ws,
+                        size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,8 @@ _SIGS = {
     'him_confusion_workspace': (c_size_t, [c_int]),
     'him_confusion': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P,
                               c_size_t, P]),
+    'him_label_instances_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'him_label_instances': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

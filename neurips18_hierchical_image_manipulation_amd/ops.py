@@ -2399,6 +2399,106 @@ def inst_summary(inst, cls, min_id=1000, max_objects=1024):
     return host[2:2 + 7 * count].reshape(count, 7).copy()
 
 
+# -- instance labelling of layouts: connected components of the classes that have instances (include/him.h) -------------
+CITYSCAPES_THINGS = tuple(range(24, 34))
+CCL_OVERFLOW, CCL_CLS_RANGE = 1, 2
+_CCL_FLAGS = ((CCL_OVERFLOW, 'plane %(plane)d: %(count)d objects, more than max_objects=%(max)d or than the ids '
+                             '%(base)d..65535 hold'),
+              (CCL_CLS_RANGE, 'plane %(plane)d: a class value outside 0..255 (or not integral)'))
+_CCL_STATE = {}         # (B, H, W, device index) -> workspace, status, pinned host copy, event, stream, things -> table
+
+
+def _ccl_things(things):
+    try:
+        ids = tuple(sorted(set(int(c) for c in things)))
+    except (TypeError, ValueError):
+        raise ValueError('label_instances: things must be an iterable of class ids')
+    for c in ids:
+        if not 0 <= c <= 255:
+            raise ValueError('label_instances: thing class %d outside 0..255' % c)
+    return ids
+
+
+def _ccl_planes(label):
+    if not torch.is_tensor(label) or not label.is_cuda:
+        raise ValueError('label_instances: label must be a device tensor')
+    if label.dtype not in _CLS_KINDS:
+        raise ValueError('label_instances: label is %s, accepted: %s' % (label.dtype,
+                                                                         ' / '.join(str(k) for k in _CLS_KINDS)))
+    ok = label.dim() in (2, 3) or (label.dim() == 4 and label.shape[1] == 1)
+    if not ok or 0 in label.shape:
+        raise ValueError('label_instances: label must be (H, W), (B, H, W) or (B, 1, H, W), got %s' % (tuple(label.shape),))
+    H, W = label.shape[-2:]
+    if H * W > 0x7fffffff:
+        raise ValueError('label_instances: %d x %d pixels (at most 2^31 - 1)' % (H, W))
+    return label.detach().reshape(-1, H, W).contiguous()
+
+
+def label_instances_launch(label, things, connectivity=4, min_area=1, base_id=1000, max_objects=1024):
+    """Queue the labelling of one (H, W) plane or a (B, H, W) / (B, 1, H, W) batch of class planes on the current stream;
+    returns ``(inst, counts, state)``: a fresh int32 device tensor of the input's shape, the device view of the per-plane
+    object counts and the cached per-shape state whose ``out`` tensor (B rows of count, flags) the kernels fill.  No
+    copy, no host synchronisation (``label_instances`` adds both).  ``counts`` and ``out`` are overwritten by the next
+    launch of the same batch shape on that device."""
+    ids = _ccl_things(things)
+    planes = _ccl_planes(label)
+    B, H, W = planes.shape
+    connectivity, min_area, base_id, max_objects = int(connectivity), int(min_area), int(base_id), int(max_objects)
+    if connectivity not in (4, 8):
+        raise ValueError('label_instances: connectivity must be 4 or 8, got %d' % connectivity)
+    if base_id < 256:
+        raise ValueError('label_instances: base_id must be at least 256, got %d' % base_id)
+    if not 1 <= max_objects <= 65536:
+        raise ValueError('label_instances: max_objects must be in 1..65536, got %d' % max_objects)
+    with torch.cuda.device(planes.device):
+        key = (B, H, W, torch.cuda.current_device())
+        st = _CCL_STATE.get(key)
+        if st is None:
+            nws = int(lib.him_label_instances_workspace(B, H, W))
+            if nws == 0:
+                raise ValueError('label_instances: a batch of %d planes of %d x %d is too large' % (B, H, W))
+            st = _CCL_STATE[key] = dict(
+                ws=torch.empty(nws, dtype=torch.uint8, device=planes.device), nws=nws,
+                out=torch.empty((B, 2), dtype=torch.int32, device=planes.device),
+                host=torch.empty((B, 2), dtype=torch.int32, pin_memory=True),
+                event=torch.cuda.Event(), stream=None, things={})
+        elif st['stream'] != _stream():
+            torch.cuda.current_stream().wait_event(st['event'])      # the previous user of this workspace, elsewhere
+        table = st['things'].get(ids)
+        if table is None:
+            host = torch.zeros(256, dtype=torch.uint8)
+            if ids:
+                host[list(ids)] = 1
+            table = st['things'][ids] = host.to(planes.device)
+        inst = torch.empty(label.shape, dtype=torch.int32, device=planes.device)
+        lib.him_label_instances(_p(planes), _CLS_KINDS[planes.dtype], B, H, W, _p(table), connectivity, min_area, base_id,
+                                max_objects, _p(inst), _p(st['out']), _p(st['ws']), st['nws'], _stream())
+        st['stream'] = _stream()
+        st['event'].record(torch.cuda.current_stream())
+    return inst, st['out'][:, 0], st
+
+
+def label_instances(label, things, connectivity=4, min_area=1, base_id=1000, max_objects=1024):
+    """``(inst, counts)``: the instance plane(s) of the class plane(s) ``label`` (uint8 / int32 / int64 / integral fp32
+    device tensor, (H, W), (B, H, W) or (B, 1, H, W)) in the Cityscapes convention, and the host ``int32`` array of the
+    objects found per plane.  Every maximal ``connectivity``-connected set of at least ``min_area`` pixels of one class
+    of ``things`` is an object; objects of a plane get the ids ``base_id``, ``base_id + 1``, ... in raster order of their
+    first pixel, every other pixel keeps its class id.  ``inst`` is int32, of the input's shape, on the device.  One
+    asynchronous copy of the status into a pinned buffer and one wait on the current stream.  ``ValueError`` names an
+    overflow or a class outside its domain."""
+    inst, _, st = label_instances_launch(label, things, connectivity, min_area, base_id, max_objects)
+    with torch.cuda.device(inst.device):
+        st['host'].copy_(st['out'], non_blocking=True)
+        st['event'].record(torch.cuda.current_stream())
+        torch.cuda.current_stream().synchronize()
+    host = st['host'].numpy().copy()
+    why = [text % dict(plane=b, count=int(host[b, 0]), max=int(max_objects), base=int(base_id))
+           for b in range(host.shape[0]) for bit, text in _CCL_FLAGS if int(host[b, 1]) & bit]
+    if why:
+        raise ValueError('label_instances: ' + '; '.join(why))
+    return inst, host[:, 0].copy()
+
+
 # -- ADE20K segmentation decode: preprocess_ade's per-image work in one device call (include/him.h) ---------------------
 _ADE_STATE = {}         # device index -> workspace, status + table, pinned host copy, event, stream, keep tuple -> tensor
 

@@ -81,6 +81,23 @@ def inst_info(inst, label, min_id=MIN_ID):
     return rows_to_info(inst.shape[-2], inst.shape[-1], rows)
 
 
+def layout_info(label, things, connectivity=4, min_area=1):
+    """``(inst, info)`` of a layout that has no instance annotation, e.g. the canvas ``JointInference.gen_layout``
+    returns: ``inst`` is the int32 device instance plane ``ops.label_instances`` derives from the class plane ``label``
+    (one (H, W) plane in any shape ``inst_info`` takes; every connected region of a class of ``things`` becomes an
+    object with an id from ``MIN_ID`` up), ``info`` the dict ``inst_info`` builds from it.  Writes no file."""
+    from . import ops
+    inst, _ = ops.label_instances(label, things, connectivity=connectivity, min_area=min_area, base_id=MIN_ID,
+                                  max_objects=MAX_OBJECTS)
+    return inst, inst_info(inst, label, min_id=MIN_ID)
+
+
+def layout_objects(info):
+    """The ``[{'bbox': [xmin, ymin, xmax, ymax], 'cls': c}, ...]`` list ``JointInference.sample_bbox`` takes as
+    ``bbox_originals``, from an ``inst_info`` / ``layout_info`` dict or a loaded ``<phase>_bbox`` file."""
+    return [{'bbox': [int(v) for v in o['bbox']], 'cls': int(o['cls'])} for o in info['objects'].values()]
+
+
 def construct_box(inst_root, inst_name, cls_name, dst, device=None):
     """For every (instance map, class map) pair ``<inst_root>/*/<inst_name>``, ``<inst_root>/*/<cls_name>`` (each list
     sorted, then zipped) write ``<dst>/<instance file stem>.json``.  Files are decoded on a small thread pool a few pairs
