@@ -545,6 +545,16 @@ int him_div_scalar_bwd(const float* W, const float* sigma, const float* dout, fl
  * ------------------------------------------------------------------------------------------- */
 int him_data_nearest(const void* base, const long long* off, const int* pitch, const int* xtab, const int* ytab,
                      int src_kind, void* dst, int dst_kind, int B, int H, int W, void* stream);
+/* him_data_nearest over a map kept as per-row run lists in a resident pack (preprocess_pack.py, INTEGRATION.md "Packed
+ * dataset"): sample b's image has int32 arrays row_start[h+1] / run_x[n] / run_v[n] at byte offsets row_off[b] /
+ * runx_off[b] / runv_off[b] from `base` (4-byte aligned); the runs of row r are [row_start[r], row_start[r+1]), run_x
+ * ascends inside a row from 0.  dst[b][y][x] = run_v of the last run of row y0[b] + ytab[b][y] whose run_x is
+ * <= x0[b] + xtab[b][x]  ((x0, y0) = the window's origin inside the image), converted by dst_kind as above.  The
+ * search stays inside the row's range (an empty range gives 0).  HIM_E_INVALID before any launch for a null pointer,
+ * B / H / W <= 0 or an unknown dst_kind. */
+int him_data_nearest_rle(const void* base, const long long* row_off, const long long* runx_off,
+                         const long long* runv_off, const int* x0, const int* y0, const int* xtab, const int* ytab,
+                         void* dst, int dst_kind, int B, int H, int W, void* stream);
 int him_data_bicubic_h(const void* base, const long long* off, const int* pitch, const int* rows, const int* first,
                        const int* count, const int* weights, int ksize, unsigned char* tmp, int maxrows, int B, int W,
                        void* stream);

@@ -38,6 +38,97 @@ __global__ void data_nearest_kernel(const unsigned char* __restrict__ base, cons
   }
 }
 
+// The same gather from a map kept as per-row run lists (preprocess_pack.py): image b has row_start[h+1] (runs of row r
+// are [row_start[r], row_start[r+1])), run_x[n] (first column of a run, 0 for the first run of a row, ascending inside
+// a row) and run_v[n] (its value), each at a byte offset from `base`.  out[b][y][x] = value of the last run of row
+// y0[b] + ytab[b][y] whose start is <= x0[b] + xtab[b][x].  A lane owns RLE_PX adjacent outputs of one row: it searches
+// the row's runs for the first, and keeps the run it found for the next ones while their column stays inside it (xtab
+// is monotone, so neighbours mostly share a run); otherwise it searches again.  The search never leaves the row's
+// [row_start[r], row_start[r+1]); an empty range gives 0.  `vec` (host: W % RLE_PX == 0 and dst aligned to RLE_PX
+// elements): the lane's outputs leave in one store; otherwise element stores, bounds-checked.
+#define RLE_PX 4
+
+template <typename T>
+__device__ __forceinline__ void rle_store(void* __restrict__ dst, long long i0, int m, bool vec, const T v[RLE_PX]) {
+  if (vec) {
+    struct alignas(RLE_PX * sizeof(T)) Q { T a[RLE_PX]; };
+    Q q;
+#pragma unroll
+    for (int k = 0; k < RLE_PX; ++k) q.a[k] = v[k];
+    *(Q*)((T*)dst + i0) = q;
+  } else {
+#pragma unroll
+    for (int k = 0; k < RLE_PX; ++k)
+      if (k < m) ((T*)dst)[i0 + k] = v[k];
+  }
+}
+
+__global__ void data_nearest_rle_kernel(const unsigned char* __restrict__ base, const long long* __restrict__ row_off,
+                                        const long long* __restrict__ runx_off, const long long* __restrict__ runv_off,
+                                        const int* __restrict__ x0, const int* __restrict__ y0,
+                                        const int* __restrict__ xtab, const int* __restrict__ ytab,
+                                        void* __restrict__ dst, int dst_kind, int vec, int B, int H, int W) {
+  const int gw = (W + RLE_PX - 1) / RLE_PX;  // groups per output row
+  const long long groups = (long long)B * H * gw;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const int xg = (int)(g % gw) * RLE_PX;
+    const long long r = g / gw;
+    const int y = (int)(r % H);
+    const int b = (int)(r / H);
+    const int m = W - xg < RLE_PX ? W - xg : RLE_PX;  // outputs of this group inside the row
+    const int* rs = (const int*)(base + row_off[b]);
+    const int* rx = (const int*)(base + runx_off[b]);
+    const int* rv = (const int*)(base + runv_off[b]);
+    const int row = y0[b] + ytab[b * H + y];
+    const int lo = rs[row], hi = rs[row + 1];
+    int xs = 1, xe = 0, val = 0;  // the run in hand covers columns [xs, xe): none yet
+    int v[RLE_PX];
+#pragma unroll
+    for (int k = 0; k < RLE_PX; ++k) {
+      v[k] = 0;
+      if (k < m) {
+        const int col = x0[b] + xtab[b * W + xg + k];
+        if ((col < xs || col >= xe) && hi > lo) {
+          int a = lo, n = hi - lo;  // the answer lies in [a, a + n)
+          while (n > 1) {
+            const int h = n >> 1;
+            if (rx[a + h] <= col) { a += h; n -= h; } else n = h;
+          }
+          xs = rx[a];
+          xe = a + 1 < hi ? rx[a + 1] : 0x7fffffff;
+          val = rv[a];
+        }
+        v[k] = val;
+      }
+    }
+    const long long i0 = ((long long)b * H + y) * W + xg;
+    switch (dst_kind) {  // the conversions of data_nearest_kernel
+      case 0: {
+        float f[RLE_PX];
+#pragma unroll
+        for (int k = 0; k < RLE_PX; ++k) f[k] = (float)v[k];
+        rle_store(dst, i0, m, vec != 0, f);
+        break;
+      }
+      case 1: {
+        float f[RLE_PX];
+#pragma unroll
+        for (int k = 0; k < RLE_PX; ++k) f[k] = __fdiv_rn((float)v[k], 255.f);
+        rle_store(dst, i0, m, vec != 0, f);
+        break;
+      }
+      case 2: {
+        unsigned char c[RLE_PX];
+#pragma unroll
+        for (int k = 0; k < RLE_PX; ++k) c[k] = (unsigned char)v[k];
+        rle_store(dst, i0, m, vec != 0, c);
+        break;
+      }
+      default: rle_store(dst, i0, m, vec != 0, v); break;
+    }
+  }
+}
+
 // horizontal pass over interleaved RGB bytes: tmp[b][r][i][c] = clip8(2^21 + sum_k w[b][i][k] * src_b[r][first+k][c])
 __global__ void data_bicubic_h_kernel(const unsigned char* __restrict__ base, const long long* __restrict__ off,
                                       const int* __restrict__ pitch, const int* __restrict__ rows,
@@ -904,6 +995,21 @@ int him_data_nearest(const void* base, const long long* off, const int* pitch, c
     default: return fail(HIM_E_INVALID, "data_nearest: src_kind %d", src_kind);
   }
   return check_launch("data_nearest");
+}
+
+int him_data_nearest_rle(const void* base, const long long* row_off, const long long* runx_off,
+                         const long long* runv_off, const int* x0, const int* y0, const int* xtab, const int* ytab,
+                         void* dst, int dst_kind, int B, int H, int W, void* stream) {
+  if (!base || !row_off || !runx_off || !runv_off || !x0 || !y0 || !xtab || !ytab || !dst)
+    return fail(HIM_E_INVALID, "data_nearest_rle: null pointer");
+  if (B <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "data_nearest_rle: bad shape");
+  if (dst_kind < 0 || dst_kind > 3) return fail(HIM_E_INVALID, "data_nearest_rle: dst_kind %d", dst_kind);
+  const size_t elem = dst_kind == 2 ? 1 : 4;
+  const int vec = W % RLE_PX == 0 && (uintptr_t)dst % (RLE_PX * elem) == 0;
+  const long long groups = (long long)B * H * ((W + RLE_PX - 1) / RLE_PX);
+  hipLaunchKernelGGL(data_nearest_rle_kernel, data_grid(groups), dim3(256), 0, ST, (const unsigned char*)base, row_off,
+                     runx_off, runv_off, x0, y0, xtab, ytab, dst, dst_kind, vec, B, H, W);
+  return check_launch("data_nearest_rle");
 }
 
 int him_data_bicubic_h(const void* base, const long long* off, const int* pitch, const int* rows, const int* first,

@@ -25,6 +25,8 @@ def CreateDataset(opt):
     from .segmentation_dataset import DATASETS
     if opt.dataloader not in DATASETS:
         raise ValueError('unknown --dataloader %r (%s)' % (opt.dataloader, ' | '.join(sorted(DATASETS))))
+    if getattr(opt, 'packed_dataroot', None):            # a resident pack (data/packed_dataset.py) instead of the files
+        from .packed_dataset import PACKED_DATASETS as DATASETS
     dataset = DATASETS[opt.dataloader]()
     print("dataset [%s] was created" % (dataset.name()))
     dataset.initialize(opt)
@@ -90,9 +92,11 @@ class CustomDatasetDataLoader(BaseDataLoader):
     def initialize(self, opt):
         BaseDataLoader.initialize(self, opt)
         self.dataset = CreateDataset(opt)
+        # a packed dataset's host stage is a few random draws: it runs in this process, --nThreads is ignored
+        workers = 0 if getattr(opt, 'packed_dataroot', None) else int(opt.nThreads)
         self.host_loader = torch.utils.data.DataLoader(
             _HostStage(self.dataset), batch_size=opt.batchSize, shuffle=not opt.serial_batches,
-            num_workers=int(opt.nThreads), collate_fn=list)
+            num_workers=workers, collate_fn=list)
         self.dataloader = _DeviceBatches(self.dataset, self.host_loader)
 
     def load_data(self):

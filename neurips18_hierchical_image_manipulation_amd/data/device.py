@@ -77,24 +77,41 @@ class MapPlan(object):
             windows = self.windows = [w.astype(np.int32) for w in windows]
             kinds = {2}
         self.kind = kinds.pop()
+        self.dtype = self.windows[0].dtype
 
-    def stage(self, st):
-        B = len(self.windows)
+    # where the pixels are: a subclass whose windows already lie in device memory overrides these three
+    def shape(self, b):
+        return self.windows[b].shape
+
+    def place(self, st, b):
+        """(byte offset from ``source(base)``, pixels per source row) of window ``b``."""
+        return st.add(self.windows[b]), self.windows[b].shape[1]
+
+    def source(self, base):
+        return base
+
+    def tables(self, B):
         xt = np.empty((B, self.W), np.int32)
         yt = np.empty((B, self.H), np.int32)
-        offs, pitch = np.empty(B, np.int64), np.empty(B, np.int32)
-        for b, w in enumerate(self.windows):
-            h_in, w_in = w.shape
+        for b in range(B):
+            h_in, w_in = self.shape(b)
             x = resample.nearest_table(w_in, self.W, self.sixteen[b])
             xt[b] = x[::-1] if self.flips[b] else x
             yt[b] = resample.nearest_table(h_in, self.H, self.sixteen[b])
-            offs[b], pitch[b] = st.add(w), w_in
+        return xt, yt
+
+    def stage(self, st):
+        B = len(self.flips)
+        xt, yt = self.tables(B)
+        offs, pitch = np.empty(B, np.int64), np.empty(B, np.int32)
+        for b in range(B):
+            offs[b], pitch[b] = self.place(st, b)
         self.at = (st.add(offs), st.add(pitch), st.add(xt), st.add(yt))
 
     def run(self, base, dst, dst_kind, stream):
         o, p, x, y = (base + a for a in self.at)
-        lib.him_data_nearest(base, o, p, x, y, self.kind, dst.data_ptr(), dst_kind, len(self.windows), self.H, self.W,
-                             stream)
+        lib.him_data_nearest(self.source(base), o, p, x, y, self.kind, dst.data_ptr(), dst_kind, len(self.flips), self.H,
+                             self.W, stream)
 
 
 class PhotoPlan(object):
@@ -103,10 +120,20 @@ class PhotoPlan(object):
     def __init__(self, windows, H, W, flips, normalize):
         self.windows, self.H, self.W, self.flips, self.normalize = windows, H, W, flips, normalize
 
+    # as MapPlan's: a subclass whose windows already lie in device memory overrides these three
+    def shape(self, b):
+        return self.windows[b].shape[:2]
+
+    def place(self, st, b):
+        return st.add(self.windows[b]), self.windows[b].shape[1]
+
+    def source(self, base):
+        return base
+
     def stage(self, st):
-        B = len(self.windows)
-        tabs = [(resample.bicubic_tables(w.shape[1], self.W), resample.bicubic_tables(w.shape[0], self.H))
-                for w in self.windows]
+        B = len(self.flips)
+        shapes = [self.shape(b) for b in range(B)]
+        tabs = [(resample.bicubic_tables(w, self.W), resample.bicubic_tables(h, self.H)) for h, w in shapes]
         self.ksx = max(t[0][3] for t in tabs)
         self.ksy = max(t[1][3] for t in tabs)
         fx, nx = np.zeros((B, self.W), np.int32), np.zeros((B, self.W), np.int32)
@@ -114,19 +141,19 @@ class PhotoPlan(object):
         wx = np.zeros((B, self.W, self.ksx), np.int32)
         wy = np.zeros((B, self.H, self.ksy), np.int32)
         offs, pitch, rows = np.empty(B, np.int64), np.empty(B, np.int32), np.empty(B, np.int32)
-        for b, (w, (tx, ty)) in enumerate(zip(self.windows, tabs)):
+        for b, (tx, ty) in enumerate(tabs):
             fx[b], nx[b], wx[b, :, :tx[3]] = tx[0], tx[1], tx[2]
             fy[b], ny[b], wy[b, :, :ty[3]] = ty[0], ty[1], ty[2]
-            offs[b], pitch[b], rows[b] = st.add(w), w.shape[1], w.shape[0]
+            (offs[b], pitch[b]), rows[b] = self.place(st, b), shapes[b][0]
         self.maxrows = int(rows.max())
         self.at = tuple(st.add(a) for a in (offs, pitch, rows, fx, nx, wx, fy, ny, wy,
                                             np.asarray(self.flips, np.int32)))
 
     def run(self, base, dst, stream):
-        B = len(self.windows)
+        B = len(self.flips)
         o, p, r, fx, nx, wx, fy, ny, wy, fl = (base + a for a in self.at)
         tmp = torch.empty((B, self.maxrows, self.W, 3), dtype=torch.uint8, device=dst.device)
-        lib.him_data_bicubic_h(base, o, p, r, fx, nx, wx, self.ksx, tmp.data_ptr(), self.maxrows, B, self.W, stream)
+        lib.him_data_bicubic_h(self.source(base), o, p, r, fx, nx, wx, self.ksx, tmp.data_ptr(), self.maxrows, B, self.W, stream)
         lib.him_data_bicubic_v(tmp.data_ptr(), self.maxrows, fy, ny, wy, self.ksy, fl, dst.data_ptr(),
                                1 if self.normalize else 0, B, self.H, self.W, stream)
         return tmp
@@ -154,6 +181,33 @@ def resize_maps(windows, H, W, flips=None, out='float', dev=None):
     kind, dtype = _MAP_OUT[out]
     dst = torch.empty((B, 1, H, W), dtype=dtype, device=dev)
     run_plans(dev, [plan], lambda base, stream: plan.run(base, dst, kind, stream))
+    return dst
+
+
+def nearest_rle(store, row_off, runx_off, runv_off, x0, y0, xtab, ytab, dst, out='float'):
+    """``him_data_nearest_rle`` on device tensors: ``store`` (uint8) holds the run lists, ``row_off`` / ``runx_off`` /
+    ``runv_off`` (B, int64) their byte offsets per sample, ``x0`` / ``y0`` (B, int32) the window origins, ``xtab`` (B,W)
+    and ``ytab`` (B,H) int32 the NEAREST tables; writes ``dst`` (B,1,H,W) of the type ``out`` names (see resize_maps)."""
+    if out not in _MAP_OUT:
+        raise ValueError('unknown output kind %r (%s)' % (out, ' | '.join(sorted(_MAP_OUT))))
+    kind, dtype = _MAP_OUT[out]
+    named = (('store', store, torch.uint8), ('row_off', row_off, torch.int64), ('runx_off', runx_off, torch.int64),
+             ('runv_off', runv_off, torch.int64), ('x0', x0, torch.int32), ('y0', y0, torch.int32),
+             ('xtab', xtab, torch.int32), ('ytab', ytab, torch.int32), ('dst', dst, dtype))
+    for name, t, want in named:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError('nearest_rle: %s must be a device tensor (the kernel reads device memory)' % name)
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError('nearest_rle: %s must be a contiguous %s tensor, got %s' % (name, want, t.dtype))
+    if dst.dim() != 4 or dst.shape[1] != 1:
+        raise ValueError('nearest_rle: dst must be (B,1,H,W), got %s' % (tuple(dst.shape),))
+    B, _, H, W = dst.shape
+    if tuple(xtab.shape) != (B, W) or tuple(ytab.shape) != (B, H) or any(t.numel() != B for t in (row_off, runx_off,
+                                                                                                runv_off, x0, y0)):
+        raise ValueError('nearest_rle: the tables do not fit dst %s' % (tuple(dst.shape),))
+    lib.him_data_nearest_rle(store.data_ptr(), row_off.data_ptr(), runx_off.data_ptr(), runv_off.data_ptr(),
+                             x0.data_ptr(), y0.data_ptr(), xtab.data_ptr(), ytab.data_ptr(), dst.data_ptr(), kind, B, H,
+                             W, torch.cuda.current_stream(dst.device).cuda_stream)
     return dst
 
 

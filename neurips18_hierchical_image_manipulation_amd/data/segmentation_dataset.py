@@ -24,16 +24,7 @@ _TIMES_255 = ('sun_rgbd', 'ade20k')      # loaders whose 8-bit instance maps are
 
 class SegmentationDataset(BaseDataset):
     def initialize(self, opt):
-        self.opt = opt
-        self.root = opt.dataroot
-        self.class_of_interest = []          # set by the child classes
-        self.config = {'prob_flip': 0.0 if opt.no_flip else 0.5, 'prob_bg': opt.prob_bg, 'fineSize': opt.fineSize,
-                       'preprocess_option': opt.resize_or_crop, 'min_box_size': opt.min_box_size,
-                       'max_box_size': opt.max_box_size, 'img_to_obj_ratio': opt.contextMargin,
-                       'patch_to_obj_ratio': 1.2, 'min_ctx_ratio': 1.2, 'max_ctx_ratio': 1.5}
-        self.check_config(self.config)
-        self.use_bbox = bool(getattr(opt, 'use_bbox', False))
-        self.load_image = bool(getattr(opt, 'load_image', False))
+        self._configure(opt)
         self.load_raw = bool(getattr(opt, 'load_raw', False))
         split = lambda suffix: os.path.join(opt.dataroot, opt.phase + suffix)
         self.dir_A = split('_A' if opt.label_nc == 0 else '_label')
@@ -46,6 +37,20 @@ class SegmentationDataset(BaseDataset):
         self.dir_bbox = split('_bbox')
         self.bbox_paths = sorted(make_dataset(self.dir_bbox))
         self.dataset_size = len(self.A_paths)
+
+    def _configure(self, opt):
+        """The part of ``initialize`` that does not depend on where the samples come from (the packed dataset shares
+        it)."""
+        self.opt = opt
+        self.root = opt.dataroot
+        self.class_of_interest = []          # set by the child classes
+        self.config = {'prob_flip': 0.0 if opt.no_flip else 0.5, 'prob_bg': opt.prob_bg, 'fineSize': opt.fineSize,
+                       'preprocess_option': opt.resize_or_crop, 'min_box_size': opt.min_box_size,
+                       'max_box_size': opt.max_box_size, 'img_to_obj_ratio': opt.contextMargin,
+                       'patch_to_obj_ratio': 1.2, 'min_ctx_ratio': 1.2, 'max_ctx_ratio': 1.5}
+        self.check_config(self.config)
+        self.use_bbox = bool(getattr(opt, 'use_bbox', False))
+        self.load_image = bool(getattr(opt, 'load_image', False))
 
     def check_config(self, config):
         assert config['preprocess_option'] in ('scale_width', 'none', 'select_region')
@@ -99,12 +104,19 @@ class SegmentationDataset(BaseDataset):
         return rec
 
     # -- device stage -----------------------------------------------------------------------------
-    def _ids(self, windows, H, W, flips, times_255):
+    def _ids(self, dtype, times_255):
         """Label-like maps as the reference's tensors: 8-bit maps are ToTensor()/255 scaled back by 255 (exactly the
         ids) or left in [0,1]; integer-mode maps stay integers."""
-        if windows[0].dtype == np.uint8:
+        if dtype == np.uint8:
             return 'float' if times_255 else 'unit'
         return 'int32'
+
+    # where a batch's pixels come from: the records' byte windows here, a resident pack in data/packed_dataset.py
+    def _map_plan(self, records, key, H, W, flips):
+        return dv.MapPlan([r[key] for r in records], H, W, flips)
+
+    def _photo_plan(self, records, key, H, W, flips):
+        return dv.PhotoPlan([r[key] for r in records], H, W, flips, True)
 
     def assemble(self, records):
         """Batch dictionary of the reference (DataLoader default_collate of ``__getitem__`` results), on the device."""
@@ -120,12 +132,11 @@ class SegmentationDataset(BaseDataset):
         plans, work = [], []
 
         def ids(key, times_255, size=(H, W), flip=flips):
-            wins = [r[key] for r in records]
-            plan = dv.MapPlan(wins, size[0], size[1], flip)
-            if compact and key == 'label' and plan.windows[0].dtype != np.uint8:
+            plan = self._map_plan(records, key, size[0], size[1], flip)
+            if compact and key == 'label' and plan.dtype != np.uint8:
                 raise ValueError('--compact_labels needs 8-bit label files (got %s): the ids would be truncated'
-                                 % plan.windows[0].dtype)
-            out = 'uint8' if (compact and key == 'label') else self._ids(plan.windows, 0, 0, 0, times_255)
+                                 % plan.dtype)
+            out = 'uint8' if (compact and key == 'label') else self._ids(plan.dtype, times_255)
             kind, dtype = dv._MAP_OUT[out]
             dst = torch.empty((B, 1, size[0], size[1]), dtype=dtype, device=dev)
             plans.append(plan)
@@ -135,7 +146,7 @@ class SegmentationDataset(BaseDataset):
         out = {'label': ids('label', True),
                'inst': ids('inst', self.opt.dataloader in _TIMES_255)}
         if 'image' in records[0]:
-            photo = dv.PhotoPlan([r['image'] for r in records], H, W, flips, True)
+            photo = self._photo_plan(records, 'image', H, W, flips)
             out['image'] = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
             plans.append(photo)
             work.append(lambda base, stream: photo.run(base, out['image'], stream))
@@ -148,7 +159,7 @@ class SegmentationDataset(BaseDataset):
             h, w = records[0]['label_raw'].shape
             out['label_raw'] = ids('label_raw', True, (h, w), [False])
             out['inst_raw'] = ids('inst_raw', False, (h, w), [False])
-            rawp = dv.PhotoPlan([records[0]['image_raw']], h, w, [False], True)
+            rawp = self._photo_plan(records, 'image_raw', h, w, [False])
             out['image_raw'] = torch.empty((1, 3, h, w), dtype=torch.float32, device=dev)
             plans.append(rawp)
             work.append(lambda base, stream: rawp.run(base, out['image_raw'], stream))
@@ -203,9 +214,9 @@ def _dataset_with_classes(cls_name, shown_name, classes, where):
 
 
 # Cityscapes: person ... bicycle (trainId-free label ids 24-33, data/cityscape_dataset.py:8)
-CityscapeDataset = _dataset_with_classes('CityscapeDataset', 'CitiscapeDataset', range(24, 34),
-                                         'data/cityscape_dataset.py')
 # ADE20K: ids 2..38 without 3, 6, 27, 34 (data/ade20k_dataset.py:8-10)
-ADE20KDataset = _dataset_with_classes('ADE20KDataset', 'ADE20KDataset',
-                                      [c for c in range(2, 39) if c not in (3, 6, 27, 34)], 'data/ade20k_dataset.py')
+CLASSES = {'cityscape': list(range(24, 34)), 'ade20k': [c for c in range(2, 39) if c not in (3, 6, 27, 34)]}
+CityscapeDataset = _dataset_with_classes('CityscapeDataset', 'CitiscapeDataset', CLASSES['cityscape'],
+                                         'data/cityscape_dataset.py')
+ADE20KDataset = _dataset_with_classes('ADE20KDataset', 'ADE20KDataset', CLASSES['ade20k'], 'data/ade20k_dataset.py')
 DATASETS = {'cityscape': CityscapeDataset, 'ade20k': ADE20KDataset}
