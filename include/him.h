@@ -509,6 +509,24 @@ int him_fill(float* p, size_t n, float value, void* stream);
 int him_scale(float* p, size_t n, float s, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (the generator a GAN is served from), in the pass Adam already makes
+ * over the arena.  No counterpart in the reference: off unless the trainer asks for it (--ema_decay).
+ *   him_adam_ema_step: him_adam_step -- the SAME kernel body, p / m / v come out bit-identical -- followed, per element
+ *     and in fp32, by  ema' = fma(w, p' - ema, ema)  with w = (float)(1.0 - ema_decay) derived in double and rounded
+ *     once (the lerp form: d * ema + (1 - d) * p' loses the whole update at d = 0.999).  ema_decay == 0 stores p' itself.
+ *     One more read and one more write per parameter: 36 B instead of 28 B.
+ *   him_ema_update: the same EMA arithmetic on its own, for tensors that change outside an Adam run.
+ *   him_swap: exchanges two fp32 buffers in place (the averaged weights go under the live parameter views and come
+ *     out again without a third buffer).
+ * Any n, pointers need only be 4-byte aligned.  HIM_E_INVALID: step < 1, ema_decay outside [0, 1), a null pointer with
+ * n > 0.  n == 0 is HIM_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+int him_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double beta1,
+                      double beta2, double eps, int step, double ema_decay, void* stream);
+int him_ema_update(float* ema, const float* p, size_t n, double ema_decay, void* stream);
+int him_swap(float* a, float* b, size_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Spectral norm power iteration, Ip = 1: models/sn_utils.py:8-25,62-67.
  *   v = l2n(u W), u' = l2n(W v^T), sigma = u' W v^T, with NOTHING detached: the backward
  *   differentiates through both normalisations.

@@ -179,6 +179,9 @@ _SIGS = {
     'him_resblock_bwd_data': (c_int, [_RESB, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     'him_resblock_bwd_weight': (c_int, [_RESB, c_int, P, P, P, P, c_int, P, c_size_t, P]),
     'him_adam_step': (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, P]),
+    'him_adam_ema_step': (c_int, [P, P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, c_double, P]),
+    'him_ema_update': (c_int, [P, P, c_size_t, c_double, P]),
+    'him_swap': (c_int, [P, P, c_size_t, P]),
     'him_fill': (c_int, [P, c_size_t, c_float, P]),
     'him_scale': (c_int, [P, c_size_t, c_float, P]),
     'him_sn_ws': (c_size_t, [c_int, c_int]),

@@ -14,9 +14,20 @@ char* err_buf() {
 // torch.optim.Adam single-tensor semantics (torch/optim/adam.py, _single_tensor_adam):
 //   exp_avg.lerp_(grad, 1-beta1); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
 //   denom = exp_avg_sq.sqrt() / sqrt(bias_correction2) + eps;  param.addcdiv_(exp_avg, denom, value=-lr/bc1)
+// Exponential moving average in lerp form: ema' = ema + w * (p - ema), w = 1 - decay rounded to fp32 ONCE by the caller
+// (d * ema + (1 - d) * p loses the whole update at d = 0.999 in fp32).  The subtraction and the FMA are spelled out so that
+// contraction cannot regroup them; w == 1 (decay 0) stores p itself -- a copy, not a lerp that rounds twice.
+__device__ __forceinline__ float ema_lerp(float ema, float p, float w) {
+  return w == 1.f ? p : __fmaf_rn(w, __fsub_rn(p, ema), ema);
+}
+
+// ONE body for him_adam_step (EMA = false) and him_adam_ema_step (EMA = true): the Adam arithmetic is the same source, so
+// p, m, v of the two entries agree bit for bit; the EMA form adds one read and one write of the shadow value (36 instead
+// of 28 B per parameter) to the same pass.
+template <bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, size_t n, float w1, float beta2, float one_m_beta2,
-                            float bc2_sqrt, float eps, float step_size) {
+                            float* __restrict__ v, float* __restrict__ ema, size_t n, float w1, float beta2,
+                            float one_m_beta2, float bc2_sqrt, float eps, float step_size, float ema_w) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float gi = g[i];
     float mi = m[i];
@@ -26,9 +37,24 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     float vi = v[i] * beta2;
     vi = vi + one_m_beta2 * (gi * gi);
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
+    const float pi = p[i] - step_size * (mi / denom);
+    p[i] = pi;
     m[i] = mi;
     v[i] = vi;
+    if (EMA) ema[i] = ema_lerp(ema[i], pi, ema_w);
+  }
+}
+
+__global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, size_t n, float ema_w) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    ema[i] = ema_lerp(ema[i], p[i], ema_w);
+}
+
+__global__ void swap_kernel(float* __restrict__ a, float* __restrict__ b, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float t = a[i];
+    a[i] = b[i];
+    b[i] = t;
   }
 }
 
@@ -152,6 +178,27 @@ __global__ __launch_bounds__(256) void div_scalar_bwd2_kernel(const float* __res
 using namespace him;
 #define ST ((hipStream_t)stream)
 
+// Shared front end of him_adam_step / him_adam_ema_step: the hyper-parameters arrive as the DOUBLES the caller holds
+// (python floats), exactly as torch.optim.Adam sees them: torch derives 1 - beta2, the bias corrections and lr / bc1 in
+// double and only then rounds each scalar to fp32 (round 2 took floats: 1.f - 0.999f = 1.0000467e-3 instead of 1e-3, a
+// 4.7e-5 relative bias of exp_avg_sq).
+template <bool EMA>
+static int adam_launch(const char* what, float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr,
+                       double beta1, double beta2, double eps, int step, double ema_decay, void* stream) {
+  if (step < 1) return fail(HIM_E_INVALID, "adam: step must be >= 1");
+  if (EMA && !(ema_decay >= 0.0 && ema_decay < 1.0)) return fail(HIM_E_INVALID, "adam_ema: ema_decay outside [0, 1)");
+  if (!n) return HIM_OK;
+  if (!p || !g || !m || !v || (EMA && !ema)) return fail(HIM_E_INVALID, "adam: null pointer");
+  const double bc1 = 1.0 - pow(beta1, step);
+  const double bc2 = 1.0 - pow(beta2, step);
+  const float step_size = (float)(lr / bc1);
+  const float bc2_sqrt = (float)sqrt(bc2);
+  const int nb = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(adam_kernel<EMA>, dim3(nb), dim3(256), 0, ST, p, g, m, v, ema, n, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size, (float)(1.0 - ema_decay));
+  return check_launch(what);
+}
+
 extern "C" {
 
 const char* him_version(void) { return "him-hip 0.6 (round 6)"; }
@@ -161,18 +208,29 @@ const char* him_last_error(void) { return err_buf(); }
 int him_adam_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1, double beta2,
                   double eps, int step, void* stream) {
   if (!n) return HIM_OK;
-  if (step < 1) return fail(HIM_E_INVALID, "adam: step must be >= 1");
-  // Hyper-parameters arrive as the DOUBLES the caller holds (python floats), exactly as torch.optim.Adam sees them:
-  // torch derives 1 - beta2, the bias corrections and lr / bc1 in double and only then rounds each scalar to fp32
-  // (round 2 took floats: 1.f - 0.999f = 1.0000467e-3 instead of 1e-3, a 4.7e-5 relative bias of exp_avg_sq).
-  const double bc1 = 1.0 - pow(beta1, step);
-  const double bc2 = 1.0 - pow(beta2, step);
-  const float step_size = (float)(lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
+  return adam_launch<false>("adam", p, g, m, v, nullptr, n, lr, beta1, beta2, eps, step, 0.0, stream);
+}
+
+int him_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double beta1,
+                      double beta2, double eps, int step, double ema_decay, void* stream) {
+  return adam_launch<true>("adam_ema", p, g, m, v, ema, n, lr, beta1, beta2, eps, step, ema_decay, stream);
+}
+
+int him_ema_update(float* ema, const float* p, size_t n, double ema_decay, void* stream) {
+  if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return fail(HIM_E_INVALID, "ema_update: ema_decay outside [0, 1)");
+  if (!n) return HIM_OK;
+  if (!ema || !p) return fail(HIM_E_INVALID, "ema_update: null pointer");
   const int nb = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(adam_kernel, dim3(nb), dim3(256), 0, ST, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size);
-  return check_launch("adam");
+  hipLaunchKernelGGL(ema_kernel, dim3(nb), dim3(256), 0, ST, ema, p, n, (float)(1.0 - ema_decay));
+  return check_launch("ema_update");
+}
+
+int him_swap(float* a, float* b, size_t n, void* stream) {
+  if (!n) return HIM_OK;
+  if (!a || !b) return fail(HIM_E_INVALID, "swap: null pointer");
+  const int nb = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(swap_kernel, dim3(nb), dim3(256), 0, ST, a, b, n);
+  return check_launch("swap");
 }
 
 size_t him_sn_ws(int rows, int cols) { return ((size_t)2 * rows + 3 * (size_t)cols + 64) * sizeof(float); }

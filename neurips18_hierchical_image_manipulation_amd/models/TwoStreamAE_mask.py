@@ -83,10 +83,13 @@ class TwoStreamAE_mask(BaseModel):
                     self.netD = MultiscaleDiscriminator(d_nc, opt.ndf, opt.num_layers_D, opt.norm_layer, False, 2, True)
                 self.netD.to(self.device)
                 self.optimizer_D = FusedAdam(self.netD.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
+            self._ema_attach(opt, resume=False)     # this constructor loads no checkpoint when training
         else:
             # test time (reference :116-118): the generator comes from <checkpoints_dir>/<name>/<which_epoch>_net_G.pth;
             # a missing file is an error
-            self.load_network_dict(self.params_dict, None, 'G', getattr(opt, 'which_epoch', 'latest'), '')
+            # --use_ema: the averaged generator of a run trained with --ema_decay (<which_epoch>_net_G_ema.pth)
+            self.load_network_dict(self.params_dict, None, 'G_ema' if getattr(opt, 'use_ema', False) else 'G',
+                                   getattr(opt, 'which_epoch', 'latest'), '')
 
     @property
     def optimizer_G(self):
@@ -137,6 +140,7 @@ class TwoStreamAE_mask(BaseModel):
         _, comb_prob, _, obj_prob = self.netG(cond)
         if eval_mode:
             return self._labels(comb_prob, obj_prob, label_map, gate)
+        self._ema_guard()
         label = self._dev(label_map)
         zero = torch.zeros((), device=self.device)
         obj_gt = self._dev(mask_obj_inst)
@@ -340,6 +344,7 @@ class TwoStreamAE_mask(BaseModel):
     def delete_model(self, which_epoch):
         """Reference :366-369 (train_box2mask.py:142 rotates checkpoints with it)."""
         self.delete_network('G', which_epoch, self.gpu_ids)
+        self.delete_network('G_ema', which_epoch, self.gpu_ids)
         if self.use_gan:
             self.delete_network('D', which_epoch, self.gpu_ids)
 
@@ -361,9 +366,20 @@ class TwoStreamAE_mask(BaseModel):
         return d
 
     def save(self, which_epoch):
+        self._ema_guard()
         self.save_network_dict(self.params_dict, self.optimizer, 'G', which_epoch, self.gpu_ids)
         if self.use_gan:
             self.save_network(self.netD, 'D', which_epoch, self.gpu_ids)
+        if self._ema_on():
+            self._ema_save(which_epoch)
+
+    def _ema_save(self, which_epoch):
+        """The per-module layout of <epoch>_net_G.pth with the parameters averaged (loads as a net_G file after a rename)."""
+        from ..ops import join_side_stream
+        join_side_stream(self.device)
+        out = {'network': {k: self.optimizer.ema_state_dict(v) for k, v in self.params_dict.items()},
+               'optimizer': self.optimizer.state_dict()}
+        torch.save(self._ema_meta(out), self._path('G_ema', which_epoch))
 
     def update_learning_rate(self, epoch=0, data_size=0):
         if epoch > self.opt.niter:

@@ -1,7 +1,9 @@
 """``BaseModel`` with the reference's stub surface and checkpoint helpers
 (reference ``models/base_model.py:8-131``): same file naming ``<epoch>_net_<label>.pth`` and the same
 strict -> subset -> shape-matched fallback when loading."""
+import contextlib
 import os
+from collections import OrderedDict
 
 import torch
 
@@ -71,7 +73,7 @@ class BaseModel(torch.nn.Module):
         path = self._path(network_label, epoch_label, save_dir)
         if not os.path.isfile(path):
             print('%s not exists yet!' % path)
-            if network_label == 'G':
+            if network_label in ('G', 'G_ema'):
                 raise RuntimeError('Generator must exist!')
             return
         self._load_with_fallback(network, torch.load(path, map_location='cpu'), network_label)
@@ -107,7 +109,7 @@ class BaseModel(torch.nn.Module):
         path = self._path(network_label, epoch_label, save_dir)
         if not os.path.isfile(path):
             print('%s not exists yet!' % path)
-            assert network_label != 'G', 'Generator must exist!'
+            assert network_label not in ('G', 'G_ema'), 'Generator must exist!'
             return
         ck = torch.load(path, map_location='cpu')
         for k, v in network_dict.items():
@@ -117,3 +119,88 @@ class BaseModel(torch.nn.Module):
 
     def update_learning_rate(self):
         pass
+
+    # ---- exponential moving average of the generator (--ema_decay; off = none of this runs) ---------------------------
+    # The average lives in the generator's FusedAdam (optim.FusedAdam.attach_ema: the Adam kernel updates it in the pass
+    # it already makes).  It is a deterministic function of the parameter trajectory: data-parallel ranks each keep their
+    # own, identical copy and exchange nothing.  Checkpoint: <epoch>_net_G_ema.pth, the keys / shapes / dtypes of
+    # <epoch>_net_G.pth with the parameters averaged and the buffers (BatchNorm statistics, spectral-norm vectors) live;
+    # the update count and decay travel in the mapping's ``_metadata`` (as torch's own module versions do), not as keys.
+    def _ema_optimizer(self):
+        return getattr(self, 'optimizer_G', None)
+
+    def _ema_join(self):
+        """Make the current stream own the generator's weights (subclasses join their helper streams)."""
+        from ..ops import join_side_stream
+        join_side_stream(self.device)
+
+    def _ema_on(self):
+        o = self._ema_optimizer()
+        return o is not None and o.ema is not None
+
+    def _ema_guard(self):
+        o = self._ema_optimizer()
+        if o is not None and o._ema_swapped:
+            raise RuntimeError('inside ema_weights(): the generator holds its averaged weights, no training step here')
+
+    def _ema_attach(self, opt, pretrained_path='', resume=True):
+        """Called by a training constructor once the generator's optimizer exists.  ``resume``: the constructor has loaded
+        the generator of --continue_train, so the average is loaded with it."""
+        decay = float(getattr(opt, 'ema_decay', 0.0) or 0.0)
+        if decay <= 0.0:
+            return
+        o = self._ema_optimizer()
+        o.attach_ema(decay)
+        if resume and getattr(opt, 'continue_train', False):
+            path = self._path('G_ema', getattr(opt, 'which_epoch', 'latest'), pretrained_path)
+            if os.path.isfile(path):
+                self._ema_load(torch.load(path, map_location='cpu'))
+            else:
+                print('%s not found: the weight average starts from the loaded generator' % path)
+
+    def _ema_meta(self, mapping):
+        o = self._ema_optimizer()
+        out = OrderedDict(mapping)
+        out._metadata = OrderedDict(ema=dict(updates=int(o.ema_updates), decay=float(o.ema_decay)))
+        return out
+
+    def _ema_read_meta(self, loaded):
+        from ..optim import ema_warm_count
+        o = self._ema_optimizer()
+        meta = (getattr(loaded, '_metadata', None) or {}).get('ema')
+        if meta is None:
+            print('the EMA checkpoint carries no update count: continuing at the full decay %g' % o.ema_decay)
+            o.ema_updates = ema_warm_count(o.ema_decay)
+        else:
+            o.ema_updates = int(meta['updates'])
+
+    def _ema_save(self, which_epoch):
+        """Pix2PixHD layout (one state dict); TwoStreamAE_mask overrides it with its per-module dict."""
+        o = self._ema_optimizer()
+        os.makedirs(self.save_dir, exist_ok=True)
+        torch.save(self._ema_meta(o.ema_state_dict(self.netG)), self._path('G_ema', which_epoch))
+
+    def _ema_load(self, loaded):
+        self._ema_optimizer().load_ema_state_dict(self.netG, loaded)
+        self._ema_read_meta(loaded)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with model.ema_weights():`` -- the generator's parameters hold their averages inside (swapped in place under
+        the live ``nn.Parameter`` views, no third buffer) and the live weights again afterwards, also when the body raises.
+        Inference, visuals and the metrics work inside unchanged; a training step raises ``RuntimeError``."""
+        from ..ops import invalidate_panels
+        o = self._ema_optimizer()
+        if not self._ema_on():
+            raise RuntimeError('ema_weights(): no weight average (train with --ema_decay > 0)')
+        if o._ema_swapped:
+            raise RuntimeError('ema_weights() does not nest')
+        self._ema_join()
+        o.swap_ema()
+        invalidate_panels(o.arena.params)        # every cached weight panel is rebuilt from the values now in place
+        try:
+            yield self
+        finally:
+            self._ema_join()
+            o.swap_ema()
+            invalidate_panels(o.arena.params)

@@ -115,7 +115,9 @@ class Pix2PixHDModel_condImg(BaseModel):
 
         if not self.isTrain or opt.continue_train or opt.load_pretrain:
             pretrained_path = '' if not self.isTrain else opt.load_pretrain
-            self.load_network(self.netG, 'G', opt.which_epoch, pretrained_path)
+            # test time with --use_ema: the averaged generator (<epoch>_net_G_ema.pth), a missing file is an error
+            use_ema = not self.isTrain and bool(getattr(opt, 'use_ema', False))
+            self.load_network(self.netG, 'G_ema' if use_ema else 'G', opt.which_epoch, pretrained_path)
             if self.isTrain:
                 self.load_network(self.netD, 'D', opt.which_epoch, pretrained_path)
 
@@ -147,6 +149,7 @@ class Pix2PixHDModel_condImg(BaseModel):
                 params = list(self.netG.parameters())
             self.optimizer_G = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
             self.optimizer_D = FusedAdam(self.netD.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
+            self._ema_attach(opt, opt.load_pretrain)
             self.reducer_G = self.reducer_D = None
             self.comm_timing = None
             self._g_chunked = False
@@ -518,6 +521,7 @@ class Pix2PixHDModel_condImg(BaseModel):
 
     def backward_G(self):
         """optimizer_G.zero_grad(); loss_G.backward(); optimizer_G.step()   (:78-80)."""
+        self._ema_guard()
         self.optimizer_G.zero_grad()
         if self.reducer_G is not None:
             self.reducer_G.begin()
@@ -547,6 +551,7 @@ class Pix2PixHDModel_condImg(BaseModel):
         (``_wait_g_update``).  The exchange budget of this order is written down in DESIGN.md 6.  With
         ``d_backward_first`` off (``bench.py --g-backward-first``) the reference's order runs: G's exchange + Adam then
         hide under the whole of D's backward."""
+        self._ema_guard()
         data = data if data is not None else self.input
         kw = dict(label=data['label'], inst=data['inst'], image=data['image'], feat=None, mask_in=data['mask_in'],
                   mask_out=data['mask_out'], infer=infer)
@@ -809,19 +814,27 @@ class Pix2PixHDModel_condImg(BaseModel):
         self._d_update_pending = False
 
     # ------------------------------------------------------------------------------------------
+    def _ema_join(self):
+        self.sync()
+
     def save(self, which_epoch):
+        self._ema_guard()
         self.sync()
         self.save_network(self.netG, 'G', which_epoch, self.gpu_ids)
         self.save_network(self.netD, 'D', which_epoch, self.gpu_ids)
+        if self._ema_on():
+            self._ema_save(which_epoch)
 
     def delete_model(self, which_epoch):
         self.delete_network('G', which_epoch, self.gpu_ids)
+        self.delete_network('G_ema', which_epoch, self.gpu_ids)
         self.delete_network('D', which_epoch, self.gpu_ids)
 
     def update_fixed_params(self):
+        self._ema_guard()
         self.sync()
         self.optimizer_G = FusedAdam(self.netG.parameters(), lr=self.opt.lr, betas=(self.opt.beta1, 0.999),
-                                     arena=self.optimizer_G.arena)
+                                     arena=self.optimizer_G.arena).adopt_ema(self.optimizer_G)
         print('------------ Now also finetuning global generator -----------')
 
     def update_learning_rate(self):

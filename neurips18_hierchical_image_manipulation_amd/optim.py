@@ -20,6 +20,27 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def ema_decay_at(decay, t):
+    """Decay of EMA update ``t`` (0-based count of the updates made so far): ``min(decay, (1 + t) / (10 + t))`` in double.
+    The ramp lets the first updates forget the initial weights (0.1, 0.18, ... reaches 0.999 at t = 8991)."""
+    return min(float(decay), (1.0 + t) / (10.0 + t))
+
+
+def ema_warm_count(decay):
+    """The smallest update count from which ``ema_decay_at`` returns ``decay`` itself."""
+    t = 0
+    while (1.0 + t) / (10.0 + t) < float(decay):
+        t = t * 2 + 1
+    lo, hi = t // 2, t
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if (1.0 + mid) / (10.0 + mid) < float(decay):
+            lo = mid + 1
+        else:
+            hi = mid
+    return lo
+
+
 class FlatArena(object):
     def __init__(self, params):
         self.params = [p for p in params]
@@ -80,6 +101,85 @@ class FusedAdam(object):
         self.exp_avg = torch.zeros_like(self.arena.data)
         self.exp_avg_sq = torch.zeros_like(self.arena.data)
         self.step_count = 0
+        # weight EMA (attach_ema): off = no buffer, and _adam calls him_adam_step exactly as without the feature
+        self.ema = None
+        self.ema_decay = 0.0
+        self.ema_updates = 0          # EMA updates made so far (the ``t`` of ema_decay_at)
+        self._ema_now = 0.0           # the decay of the step in flight: ONE value for all ranges of a step
+        self._ema_swapped = False     # inside swap_ema() ... swap_ema(): the arena holds the averaged values
+
+    # ---- exponential moving average of the arena, computed by the Adam kernel itself (him_adam_ema_step) ----
+    def attach_ema(self, decay, ema=None, updates=0):
+        """From now on every Adam run also averages the elements it updates: ``self.ema`` (one more arena-sized buffer,
+        4 B per parameter) starts as a copy of the parameters, or as ``ema`` with ``updates`` updates behind it (a buffer
+        handed over from another optimizer over the same arena, or read from a checkpoint)."""
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError('ema decay %r: a value in (0, 1)' % decay)
+        if getattr(self, '_done', None) is not None:
+            raise RuntimeError('attach_ema inside an open piecewise step')
+        if ema is None:
+            ema = self.arena.data.clone()
+        elif ema.shape != self.arena.data.shape or ema.dtype != torch.float32 or ema.device != self.arena.data.device:
+            raise ValueError('the EMA buffer does not match the arena')
+        self.ema, self.ema_decay, self.ema_updates = ema, decay, int(updates)
+        return self
+
+    def reset_ema(self):
+        """Restart the average from the parameters as they are now (they were loaded after the optimizer was built)."""
+        if self.ema is not None:
+            self.ema.copy_(self.arena.data)
+            self.ema_updates = 0
+
+    def adopt_ema(self, other):
+        """Take over ``other``'s EMA buffer and update count (an optimizer rebuilt over the same arena)."""
+        if other.ema is not None:
+            if other.arena is not self.arena:
+                raise ValueError('adopt_ema: the two optimizers walk different arenas')
+            self.attach_ema(other.ema_decay, other.ema, other.ema_updates)
+        return self
+
+    def _ema_open(self):
+        if self.ema is not None:
+            self._ema_now = ema_decay_at(self.ema_decay, self.ema_updates)
+            self.ema_updates += 1
+
+    def _check_live(self):
+        if self._ema_swapped:
+            raise RuntimeError('the arena holds the averaged weights (inside ema_weights()): no optimizer step here')
+
+    def swap_ema(self):
+        """Exchange the parameters and their averages in place (one kernel over the arena, current stream).  The caller
+        owns the stream order and the weight panels (see the models' ``ema_weights``); while swapped, stepping raises."""
+        if self.ema is None:
+            raise RuntimeError('no EMA attached (ema_decay 0)')
+        if getattr(self, '_done', None) is not None:
+            raise RuntimeError('swap_ema inside an open piecewise step')
+        lib.him_swap(self.arena.data.data_ptr(), self.ema.data_ptr(), self.arena.total, _stream())
+        self._ema_swapped = not self._ema_swapped
+
+    def ema_state_dict(self, network):
+        """``network.state_dict()`` on the host with every arena parameter replaced by its average (buffers: live)."""
+        by_id = {id(p): o for p, o in zip(self.arena.params, self.arena.offsets)}
+        names = {k: by_id[id(p)] for k, p in network.named_parameters() if id(p) in by_id}
+        src = self.arena.data if self._ema_swapped else self.ema
+        out = {}
+        for k, v in network.state_dict().items():
+            if k in names:
+                out[k] = src[names[k]:names[k] + v.numel()].view(v.shape).detach().cpu().clone()
+            else:
+                out[k] = v.detach().cpu().clone()
+        return out
+
+    def load_ema_state_dict(self, network, sd):
+        """Fill the EMA buffer from a checkpoint with ``network``'s keys (what ``ema_state_dict`` wrote)."""
+        by_id = {id(p): o for p, o in zip(self.arena.params, self.arena.offsets)}
+        for k, p in network.named_parameters():
+            if id(p) in by_id:
+                if k not in sd or tuple(sd[k].shape) != tuple(p.shape):
+                    raise ValueError('EMA checkpoint: %s is missing or has another shape' % k)
+                o = by_id[id(p)]
+                self.ema[o:o + p.numel()].copy_(sd[k].reshape(-1))
 
     def zero_grad(self, set_to_none=False):
         self.arena.zero_grad()
@@ -108,7 +208,9 @@ class FusedAdam(object):
         if getattr(self, '_done', None):
             raise RuntimeError('a piecewise optimizer step is still open (aborted after part of the arena was updated): '
                                'step() completes it')
+        self._check_live()
         self.step_count += 1
+        self._ema_open()
         self._done = []
 
     def abort_step(self):
@@ -119,15 +221,24 @@ class FusedAdam(object):
         done = getattr(self, '_done', None)
         if done is not None and not done:
             self.step_count -= 1
+            if self.ema is not None:
+                self.ema_updates -= 1
             self._done = None
 
     def _adam(self, lo, hi):
         a = self.arena
         for (s, e, lr, b1, b2, eps) in self._runs():
             s, e = max(s, lo), min(e, hi)
-            if s < e:
+            if s >= e:
+                continue
+            if self.ema is None:
                 lib.him_adam_step(a.data.data_ptr() + 4 * s, a.grad.data_ptr() + 4 * s, self.exp_avg.data_ptr() + 4 * s,
                                   self.exp_avg_sq.data_ptr() + 4 * s, e - s, lr, b1, b2, eps, self.step_count, _stream())
+            else:       # the same pass also averages [s, e): every element exactly once per step, as Adam visits it
+                lib.him_adam_ema_step(a.data.data_ptr() + 4 * s, a.grad.data_ptr() + 4 * s,
+                                      self.exp_avg.data_ptr() + 4 * s, self.exp_avg_sq.data_ptr() + 4 * s,
+                                      self.ema.data_ptr() + 4 * s, e - s, lr, b1, b2, eps, self.step_count,
+                                      self._ema_now, _stream())
 
     def _params_in(self, lo, hi):
         a = self.arena
@@ -144,6 +255,7 @@ class FusedAdam(object):
         have run) -- the data-parallel reducer's bucket trigger (dist.GradReducer.bucket_hook)."""
         if getattr(self, '_done', None) is None:
             raise RuntimeError('step_range outside begin_step() ... step()')
+        self._check_live()
         self._adam(lo, hi)
         self._done.append((lo, hi))
         from .ops import refresh_panels
@@ -151,11 +263,13 @@ class FusedAdam(object):
 
     def step(self):
         a = self.arena
+        self._check_live()
         from .ops import join_side_stream, refresh_panels
         join_side_stream(a.grad.device)        # wait for the side-stream weight gradients
         done = getattr(self, '_done', None)
         if done is None:
             self.step_count += 1
+            self._ema_open()
             todo = [(0, a.total)]
         else:                                  # close a piecewise step: the complement of what step_range has covered
             todo, at = [], 0

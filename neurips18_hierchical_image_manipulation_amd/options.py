@@ -76,12 +76,40 @@ BOX2MASK_TEST_FLAGS = [
 # additions of this build (absent in the reference)
 BUILD_FLAGS = [('vgg_weights', str, ''), ('verbose', 'flag', False), ('color_noise', 'flag', False),
                ('compact_labels', 'flag', False),
+               # weight EMA of the generator: --ema_decay d > 0 averages it inside the Adam pass (0 = off, no buffer) and
+               # save() adds <epoch>_net_G_ema.pth; --use_ema loads that file at test time
+               ('ema_decay', float, 0.0), ('use_ema', 'flag', False),
                ('sn_D', 'flag', False)]             # spectral-norm convolutions in the multi-scale PatchGAN (sn_utils.py)   # loader: label ids as uint8 (the trainers widen them on the device)
+
+
+# The box2mask parsers keep exactly the reference's argparse tables, so the two EMA settings travel there as ``opt``
+# attributes with these defaults; ``parse`` also accepts ``--ema_decay d`` / ``--use_ema`` in the argument list (a
+# JointInference script may carry them) and takes them out before argparse sees the rest.
+EMA_ATTRS = (('ema_decay', float, 0.0), ('use_ema', 'flag', False))
+
+
+def _take_attr_flags(argv, attrs):
+    values, rest, i = {n: d for n, _, d in attrs}, [], 0
+    kinds = {'--' + n: (n, t) for n, t, _ in attrs}
+    while i < len(argv):
+        hit = kinds.get(argv[i])
+        if hit is None:
+            rest.append(argv[i])
+        elif hit[1] == 'flag':
+            values[hit[0]] = True
+        else:
+            if i + 1 >= len(argv):
+                raise SystemExit('%s expects a value' % argv[i])
+            values[hit[0]] = hit[1](argv[i + 1])
+            i += 1
+        i += 1
+    return values, rest
 
 
 class MaskToImageOptions(object):
     isTrain = False
     tables = [BASE_FLAGS, BUILD_FLAGS]
+    attrs = ()
 
     def __init__(self):
         self.parser = argparse.ArgumentParser()
@@ -99,7 +127,10 @@ class MaskToImageOptions(object):
     def parse(self, save=True, default_args=()):
         if not self.initialized:
             self.initialize()
-        self.opt = self.parser.parse_args(list(default_args))
+        extra, default_args = _take_attr_flags(list(default_args), self.attrs)
+        self.opt = self.parser.parse_args(default_args)
+        for k, v in extra.items():
+            setattr(self.opt, k, v)
         self.opt.isTrain = self.isTrain
         self.opt.gpu_ids = [int(s) for s in self.opt.gpu_ids.split(',') if int(s) >= 0]
         if save and not getattr(self.opt, 'continue_train', False):
@@ -129,6 +160,7 @@ class BoxToMaskOptions(MaskToImageOptions):
     behaviour as the mask2image parser)."""
     isTrain = False
     tables = [BOX2MASK_BASE_FLAGS]
+    attrs = EMA_ATTRS
 
 
 class BoxToMaskTrainOptions(BoxToMaskOptions):
