@@ -527,6 +527,47 @@ int him_ema_update(float* ema, const float* p, size_t n, double ema_decay, void*
 int him_swap(float* a, float* b, size_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradient guard: the global norm of a flat gradient arena, a clip coefficient and a non-finite flag, all left in
+ * DEVICE memory where the Adam kernel reads them -- no host synchronisation inside an optimizer step.  No counterpart
+ * in the reference: off unless the trainer asks for it (--clip_grad_norm / --skip_nonfinite).
+ *
+ * him_grad_stats: one pass over g[0, n) (4 B per element).
+ *   seg      device array of nseg (begin, length) pairs: sorted, non-overlapping sub-ranges of [0, n) (the arena's
+ *            parameter tensors; padding belongs to no segment).  nseg == 0: seg and seg_out may be null.
+ *   seg_out  device, 2 * nseg doubles: [2i] = sum of squares of the FINITE elements of segment i, [2i+1] = its number
+ *            of non-finite elements (Inf or NaN).
+ *   st       device, 8 doubles:  [0] sum of squares of the finite elements of [0, n)   [1] non-finite count of [0, n)
+ *            [2] sqrt(st[0])   [3] clip coefficient c   [4] calls seen   [5] calls with st[1] > 0   [6], [7] = 0.
+ *            [4] and [5] are cumulative: the caller zeroes the buffer once, every accepted call adds to them.
+ *   c        1 when max_norm <= 0 or +inf (clipping off), else min(1, max_norm / (st[2] + 1e-6)) -- the rule of
+ *            torch.nn.utils.clip_grad_norm_ -- evaluated in double and rounded to fp32 ONCE; st[3] is that fp32 value
+ *            widened back.
+ *   Every square is formed in double (exact for fp32 inputs) and every sum is a double sum.  The result is a pure
+ *   function of (g, n, seg, max_norm): no floating-point atomics, and the order of the additions is fixed by a
+ *   decomposition into chunks counted from each range's start, independent of grid size and of the device's CU count.
+ *   Loads are 16 bytes wide where the chunk is 16-byte aligned (256-byte aligned arena slots always are); any 4-byte
+ *   aligned g is correct and gives the same bits.  A seg table that breaks its contract is clamped into [0, n): wrong
+ *   sums, never an access outside g or ws.
+ *   ws: him_grad_stats_ws(n, nseg) bytes, rewritten by every call.
+ *   HIM_E_INVALID: nseg < 0, max_norm negative or NaN, null st, null seg / seg_out with nseg > 0, null g / ws with
+ *   n > 0.  HIM_E_WORKSPACE: ws_bytes too small.  A refused call writes nothing.  n == 0 reads nothing (g, ws may be
+ *   null), writes zeros and still counts as a call.
+ *
+ * him_adam_guarded_step: him_adam_step (ema == NULL; ema_decay ignored) or him_adam_ema_step (ema != NULL) -- the SAME
+ *   kernel body -- behind st[1] and st[3], read by the kernel from device memory.  st[1] > 0: nothing is stored, p / m /
+ *   v / ema keep their bits.  Otherwise the body runs on g' = fl32(g * c) with c = (float)st[3]; at c == 1 the multiply
+ *   is skipped and the results are bit-identical to the unguarded entries.  UNLIKE torch.nn.utils.clip_grad_norm_ the
+ *   gradient buffer is never modified: clipping happens in registers, g is read-only.  A caller that wants clipping
+ *   without the skip hands over an st whose slot [1] is zero.  Return codes as him_adam_ema_step, plus null st.
+ * ------------------------------------------------------------------------------------------- */
+size_t him_grad_stats_ws(size_t n, int nseg);
+int him_grad_stats(const float* g, size_t n, const long long* seg, int nseg, double* seg_out, double* st,
+                   double max_norm, void* ws, size_t ws_bytes, void* stream);
+int him_adam_guarded_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr,
+                          double beta1, double beta2, double eps, int step, double ema_decay, const double* st,
+                          void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Spectral norm power iteration, Ip = 1: models/sn_utils.py:8-25,62-67.
  *   v = l2n(u W), u' = l2n(W v^T), sigma = u' W v^T, with NOTHING detached: the backward
  *   differentiates through both normalisations.

@@ -182,6 +182,10 @@ _SIGS = {
     'him_adam_ema_step': (c_int, [P, P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, c_double, P]),
     'him_ema_update': (c_int, [P, P, c_size_t, c_double, P]),
     'him_swap': (c_int, [P, P, c_size_t, P]),
+    'him_grad_stats_ws': (c_size_t, [c_size_t, c_int]),
+    'him_grad_stats': (c_int, [P, c_size_t, P, c_int, P, P, c_double, P, c_size_t, P]),
+    'him_adam_guarded_step': (c_int, [P, P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, c_double, P,
+                                      P]),
     'him_fill': (c_int, [P, c_size_t, c_float, P]),
     'him_scale': (c_int, [P, c_size_t, c_float, P]),
     'him_sn_ws': (c_size_t, [c_int, c_int]),

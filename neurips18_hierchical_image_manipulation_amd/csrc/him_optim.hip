@@ -24,12 +24,23 @@ __device__ __forceinline__ float ema_lerp(float ema, float p, float w) {
 // ONE body for him_adam_step (EMA = false) and him_adam_ema_step (EMA = true): the Adam arithmetic is the same source, so
 // p, m, v of the two entries agree bit for bit; the EMA form adds one read and one write of the shadow value (36 instead
 // of 28 B per parameter) to the same pass.
-template <bool EMA>
+// GUARD = true is him_adam_guarded_step: the same body behind two values read from the device, `st` of him_grad_stats.
+// st[1] > 0 (a non-finite gradient element somewhere in the arena): every thread returns before its first store.
+// st[3] = the clip coefficient c as an fp32 value: the gradient enters the body as fl32(g * c), the multiply skipped at
+// c == 1 so that an unclipped guarded step has the bits of the unguarded one.  g itself is only read.
+template <bool EMA, bool GUARD>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, float* __restrict__ ema, size_t n, float w1, float beta2,
-                            float one_m_beta2, float bc2_sqrt, float eps, float step_size, float ema_w) {
+                            float one_m_beta2, float bc2_sqrt, float eps, float step_size, float ema_w,
+                            const double* __restrict__ st) {
+  float c = 1.f;
+  if (GUARD) {
+    if (st[1] > 0.0) return;
+    c = (float)st[3];
+  }
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gi = g[i];
+    float gi = g[i];
+    if (GUARD && c != 1.f) gi = __fmul_rn(gi, c);
     float mi = m[i];
     // at::lerp: weight < 0.5 ? start + weight*(end-start) : end - (end-start)*(1-weight)
     const float diff = gi - mi;
@@ -55,6 +66,228 @@ __global__ void swap_kernel(float* __restrict__ a, float* __restrict__ b, size_t
     const float t = a[i];
     a[i] = b[i];
     b[i] = t;
+  }
+}
+
+// ---- gradient statistics (him_grad_stats) ------------------------------------------------------------------------------
+// Decomposition, a function of (n, seg) alone: [0, n) is cut into R = 2 * nseg + 1 RANGES -- gap 0, segment 0, gap 1, ...,
+// segment nseg-1, tail gap (any of them may be empty) -- and every range into CHUNKS of GS_CHUNK floats counted from the
+// range's own start.  One workgroup sums one chunk (element k of the chunk belongs to thread (k / 4) % 256, whatever the
+// pointer's alignment; each thread adds its squares in index order into four double lanes, the lanes and the threads meet
+// in a fixed tree).  The finish adds the chunk partials of a segment, and of the whole list, in a fixed order.  Neither
+// grid size enters: both kernels stride over work items, and an item's value does not depend on which workgroup ran it.
+constexpr int GS_CHUNK = 16384;
+
+struct GsWork {
+  long long start, len;
+};
+
+// workspace: [ranges: R x (begin, len)] [first chunk of range r: R + 1] [work list: cap] [partials: cap x (sum, count)]
+struct GsLayout {
+  long long R, cap;
+  long long* rng;
+  long long* first;
+  GsWork* work;
+  double* part;
+};
+inline size_t gs_bytes(size_t n, int nseg) {
+  const size_t R = 2 * (size_t)nseg + 1, cap = n / GS_CHUNK + R;
+  return 8 + (2 * R + (R + 1)) * sizeof(long long) + cap * (sizeof(GsWork) + 2 * sizeof(double));
+}
+inline GsLayout gs_layout(void* ws, size_t n, int nseg) {
+  GsLayout L;
+  L.R = 2 * (long long)nseg + 1;
+  L.cap = (long long)(n / GS_CHUNK) + L.R;
+  L.rng = (long long*)(((uintptr_t)ws + 7) & ~(uintptr_t)7);
+  L.first = L.rng + 2 * L.R;
+  L.work = (GsWork*)(L.first + L.R + 1);
+  L.part = (double*)(L.work + L.cap);
+  return L;
+}
+
+__device__ __forceinline__ long long gs_clamp(long long x, long long lo, long long hi) {
+  return x < lo ? lo : (x > hi ? hi : x);
+}
+// segment i clamped into [0, n] (a table that breaks its contract gives wrong sums, never an address outside g or ws)
+__device__ __forceinline__ void gs_seg(const long long* __restrict__ seg, long long n, long long i, long long& b,
+                                       long long& e) {
+  b = gs_clamp(seg[2 * i], 0, n);
+  e = b + gs_clamp(seg[2 * i + 1], 0, n - b);
+}
+__device__ __forceinline__ void gs_range(const long long* __restrict__ seg, long long nseg, long long n, long long r,
+                                         long long& b, long long& len) {
+  long long e;
+  if (r & 1) {
+    gs_seg(seg, n, r >> 1, b, e);
+  } else {
+    const long long i = r >> 1;
+    long long pb = 0, pe = 0;
+    if (i > 0) gs_seg(seg, n, i - 1, pb, pe);
+    b = pe;
+    if (i < nseg) {
+      long long nb, ne;
+      gs_seg(seg, n, i, nb, ne);
+      e = nb > b ? nb : b;
+    } else {
+      e = n;
+    }
+  }
+  len = e - b;
+}
+
+// one workgroup: the range table, the first chunk index of every range (an integer scan) and the chunk work list
+__global__ __launch_bounds__(256) void gs_plan_kernel(const long long* __restrict__ seg, long long nseg, long long n,
+                                                      long long R, long long cap, long long* __restrict__ rng,
+                                                      long long* __restrict__ first, GsWork* __restrict__ work) {
+  __shared__ long long sh[257];
+  const int t = threadIdx.x;
+  const long long per = (R + 255) / 256;
+  const long long r0 = t * per, r1 = r0 + per < R ? r0 + per : R;
+  long long mine = 0;
+  for (long long r = r0; r < r1; ++r) {
+    long long b, len;
+    gs_range(seg, nseg, n, r, b, len);
+    rng[2 * r] = b;
+    rng[2 * r + 1] = len;
+    mine += (len + GS_CHUNK - 1) / GS_CHUNK;
+  }
+  sh[t + 1] = mine;
+  __syncthreads();
+  if (t == 0) {
+    sh[0] = 0;
+    for (int k = 1; k <= 256; ++k) sh[k] += sh[k - 1];
+  }
+  __syncthreads();
+  long long w = sh[t];
+  for (long long r = r0; r < r1; ++r) {
+    long long b, len;
+    gs_range(seg, nseg, n, r, b, len);
+    first[r] = w < cap ? w : cap;
+    for (long long o = 0; o < len; o += GS_CHUNK, ++w)
+      if (w < cap) {
+        work[w].start = b + o;
+        work[w].len = len - o < GS_CHUNK ? len - o : GS_CHUNK;
+      }
+  }
+  if (t == 255) first[R] = sh[256] < cap ? sh[256] : cap;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// fixed tree over the 256 threads; the result is valid in thread 0.  `sh` holds >= 4 doubles.
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// finite: x * x is exact in double (24 x 24 bits) and the fma rounds the sum once; Inf / NaN: counted, adds nothing
+__device__ __forceinline__ void gs_acc(float x, double& acc, unsigned& bad) {
+  if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) {
+    ++bad;
+  } else {
+    const double d = (double)x;
+    acc = fma(d, d, acc);
+  }
+}
+
+__global__ __launch_bounds__(256) void gs_partial_kernel(const float* __restrict__ g, const GsWork* __restrict__ work,
+                                                         const long long* __restrict__ first, long long R,
+                                                         double* __restrict__ part) {
+  __shared__ double sh[4];
+  const long long total = first[R];
+  for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+    const float* __restrict__ src = g + work[w].start;
+    const int len = (int)work[w].len;
+    const bool wide = ((uintptr_t)src & 15) == 0;      // uniform over the workgroup
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    unsigned bad = 0;
+    for (int k = 4 * (int)threadIdx.x; k < len; k += 1024) {
+      if (k + 4 <= len) {
+        float4 q;
+        if (wide) {
+          q = *reinterpret_cast<const float4*>(src + k);
+        } else {
+          q.x = src[k];
+          q.y = src[k + 1];
+          q.z = src[k + 2];
+          q.w = src[k + 3];
+        }
+        gs_acc(q.x, a0, bad);
+        gs_acc(q.y, a1, bad);
+        gs_acc(q.z, a2, bad);
+        gs_acc(q.w, a3, bad);
+      } else {                                         // the chunk's last, partial quad
+        gs_acc(src[k], a0, bad);
+        if (k + 1 < len) gs_acc(src[k + 1], a1, bad);
+        if (k + 2 < len) gs_acc(src[k + 2], a2, bad);
+      }
+    }
+    const double s = block_sum_f64((a0 + a1) + (a2 + a3), sh);
+    const double c = block_sum_f64((double)bad, sh);     // <= 16384: exact
+    if (threadIdx.x == 0) {
+      part[2 * w] = s;
+      part[2 * w + 1] = c;
+    }
+  }
+}
+
+// workgroup 0: the whole list -> st.  Workgroups 1..: one wavefront per segment -> seg_out.  Thread (lane) t adds the
+// partials t, t + 256 (64), ... in that order, then the fixed tree: independent of how many workgroups the launch has.
+__global__ __launch_bounds__(256) void gs_finish_kernel(const double* __restrict__ part,
+                                                        const long long* __restrict__ first, long long R, long long nseg,
+                                                        double* __restrict__ seg_out, double* __restrict__ st,
+                                                        double max_norm) {
+  __shared__ double sh[4];
+  if (blockIdx.x == 0) {
+    const long long total = first ? first[R] : 0;
+    double s = 0.0, c = 0.0;
+    for (long long w = threadIdx.x; w < total; w += 256) {
+      s += part[2 * w];
+      c += part[2 * w + 1];
+    }
+    s = block_sum_f64(s, sh);
+    c = block_sum_f64(c, sh);
+    if (threadIdx.x == 0) {
+      const double nrm = sqrt(s);
+      float coef = 1.f;
+      if (max_norm > 0.0 && max_norm < INFINITY) {
+        const double q = max_norm / (nrm + 1e-6);
+        coef = (float)(q < 1.0 ? q : 1.0);
+      }
+      const double calls = st[4], skipped = st[5];
+      st[0] = s;
+      st[1] = c;
+      st[2] = nrm;
+      st[3] = (double)coef;
+      st[4] = calls + 1.0;
+      st[5] = skipped + (c > 0.0 ? 1.0 : 0.0);
+      st[6] = 0.0;
+      st[7] = 0.0;
+    }
+    return;
+  }
+  const int lane = threadIdx.x & 63;
+  for (long long i = ((long long)blockIdx.x - 1) * 4 + (threadIdx.x >> 6); i < nseg; i += ((long long)gridDim.x - 1) * 4) {
+    double s = 0.0, c = 0.0;
+    if (first) {
+      const long long w1 = first[2 * i + 2];
+      for (long long w = first[2 * i + 1] + lane; w < w1; w += 64) {
+        s += part[2 * w];
+        c += part[2 * w + 1];
+      }
+    }
+    s = wave_sum_f64(s);
+    c = wave_sum_f64(c);
+    if (lane == 0) {
+      seg_out[2 * i] = s;
+      seg_out[2 * i + 1] = c;
+    }
   }
 }
 
@@ -182,20 +415,21 @@ using namespace him;
 // (python floats), exactly as torch.optim.Adam sees them: torch derives 1 - beta2, the bias corrections and lr / bc1 in
 // double and only then rounds each scalar to fp32 (round 2 took floats: 1.f - 0.999f = 1.0000467e-3 instead of 1e-3, a
 // 4.7e-5 relative bias of exp_avg_sq).
-template <bool EMA>
+template <bool EMA, bool GUARD = false>
 static int adam_launch(const char* what, float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr,
-                       double beta1, double beta2, double eps, int step, double ema_decay, void* stream) {
+                       double beta1, double beta2, double eps, int step, double ema_decay, void* stream,
+                       const double* st = nullptr) {
   if (step < 1) return fail(HIM_E_INVALID, "adam: step must be >= 1");
   if (EMA && !(ema_decay >= 0.0 && ema_decay < 1.0)) return fail(HIM_E_INVALID, "adam_ema: ema_decay outside [0, 1)");
   if (!n) return HIM_OK;
-  if (!p || !g || !m || !v || (EMA && !ema)) return fail(HIM_E_INVALID, "adam: null pointer");
+  if (!p || !g || !m || !v || (EMA && !ema) || (GUARD && !st)) return fail(HIM_E_INVALID, "adam: null pointer");
   const double bc1 = 1.0 - pow(beta1, step);
   const double bc2 = 1.0 - pow(beta2, step);
   const float step_size = (float)(lr / bc1);
   const float bc2_sqrt = (float)sqrt(bc2);
   const int nb = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(adam_kernel<EMA>, dim3(nb), dim3(256), 0, ST, p, g, m, v, ema, n, (float)(1.0 - beta1),
-                     (float)beta2, (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size, (float)(1.0 - ema_decay));
+  hipLaunchKernelGGL((adam_kernel<EMA, GUARD>), dim3(nb), dim3(256), 0, ST, p, g, m, v, ema, n, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size, (float)(1.0 - ema_decay), st);
   return check_launch(what);
 }
 
@@ -231,6 +465,38 @@ int him_swap(float* a, float* b, size_t n, void* stream) {
   const int nb = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
   hipLaunchKernelGGL(swap_kernel, dim3(nb), dim3(256), 0, ST, a, b, n);
   return check_launch("swap");
+}
+
+size_t him_grad_stats_ws(size_t n, int nseg) { return gs_bytes(n, nseg < 0 ? 0 : nseg); }
+
+int him_grad_stats(const float* g, size_t n, const long long* seg, int nseg, double* seg_out, double* st,
+                   double max_norm, void* ws, size_t ws_bytes, void* stream) {
+  if (nseg < 0) return fail(HIM_E_INVALID, "grad_stats: nseg < 0");
+  if (!(max_norm >= 0.0)) return fail(HIM_E_INVALID, "grad_stats: max_norm is negative or NaN");
+  if (!st) return fail(HIM_E_INVALID, "grad_stats: null st");
+  if (nseg > 0 && (!seg || !seg_out)) return fail(HIM_E_INVALID, "grad_stats: null segment table");
+  if (n > 0 && (!g || !ws)) return fail(HIM_E_INVALID, "grad_stats: null pointer");
+  if (n > 0 && ws_bytes < gs_bytes(n, nseg)) return fail(HIM_E_WORKSPACE, "grad_stats: ws too small");
+  const int nfin = 1 + (int)std::min<long long>(((long long)nseg + 3) / 4, 1024);
+  if (!n) {      // nothing to read: zeros everywhere, the call still counts
+    hipLaunchKernelGGL(gs_finish_kernel, dim3(nfin), dim3(256), 0, ST, (const double*)nullptr,
+                       (const long long*)nullptr, (long long)0, (long long)nseg, seg_out, st, max_norm);
+    return check_launch("grad_stats");
+  }
+  const GsLayout L = gs_layout(ws, n, nseg);
+  hipLaunchKernelGGL(gs_plan_kernel, dim3(1), dim3(256), 0, ST, seg, (long long)nseg, (long long)n, L.R, L.cap, L.rng,
+                     L.first, L.work);
+  hipLaunchKernelGGL(gs_partial_kernel, dim3((unsigned)std::min<long long>(L.cap, 1 << 20)), dim3(256), 0, ST, g,
+                     (const GsWork*)L.work, (const long long*)L.first, L.R, L.part);
+  hipLaunchKernelGGL(gs_finish_kernel, dim3(nfin), dim3(256), 0, ST, (const double*)L.part, (const long long*)L.first,
+                     L.R, (long long)nseg, seg_out, st, max_norm);
+  return check_launch("grad_stats");
+}
+
+int him_adam_guarded_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double beta1,
+                          double beta2, double eps, int step, double ema_decay, const double* st, void* stream) {
+  if (ema) return adam_launch<true, true>("adam_guarded", p, g, m, v, ema, n, lr, beta1, beta2, eps, step, ema_decay, stream, st);
+  return adam_launch<false, true>("adam_guarded", p, g, m, v, nullptr, n, lr, beta1, beta2, eps, step, 0.0, stream, st);
 }
 
 size_t him_sn_ws(int rows, int cols) { return ((size_t)2 * rows + 3 * (size_t)cols + 64) * sizeof(float); }

@@ -84,6 +84,7 @@ class TwoStreamAE_mask(BaseModel):
                 self.netD.to(self.device)
                 self.optimizer_D = FusedAdam(self.netD.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
             self._ema_attach(opt, resume=False)     # this constructor loads no checkpoint when training
+            self._guard_attach(opt)                 # --clip_grad_norm / --skip_nonfinite: both optimizers
         else:
             # test time (reference :116-118): the generator comes from <checkpoints_dir>/<name>/<which_epoch>_net_G.pth;
             # a missing file is an error

@@ -120,6 +120,35 @@ class BaseModel(torch.nn.Module):
     def update_learning_rate(self):
         pass
 
+    # ---- gradient guard (--clip_grad_norm F / --skip_nonfinite; off = none of this runs) -------------------------------
+    # Both optimizers get optim.FusedAdam.attach_guard: one statistics pass over the gradient arena per step, and an Adam
+    # kernel that reads the clip coefficient and the skip flag from device memory.  Nothing here synchronises.
+    def _guard_attach(self, opt):
+        """Called by a training constructor once the optimizers exist."""
+        max_norm = float(getattr(opt, 'clip_grad_norm', 0.0) or 0.0)
+        skip = bool(getattr(opt, 'skip_nonfinite', False))
+        if max_norm == 0.0 and not skip:
+            return
+        for o in (getattr(self, 'optimizer_G', None), getattr(self, 'optimizer_D', None)):
+            if o is not None:
+                o.attach_guard(max_norm, skip)
+
+    def grad_report(self):
+        """Gradient norms, clip coefficients and skipped-step counts of the last step, as host floats that merge into the
+        dict given to ``Visualizer.print_current_errors`` / ``plot_current_errors``.  It SYNCHRONISES with the device:
+        call it at print frequency only.  Without a guard (both options off) it raises."""
+        out = {}
+        self._ema_join()         # the optimizers may still be running on their own streams
+        for tag in ('G', 'D'):
+            o = getattr(self, 'optimizer_' + tag, None)
+            if o is None or o.guard is None:
+                continue
+            r = o.grad_report()
+            out[tag + '_grad_norm'], out[tag + '_clip_coef'], out[tag + '_skipped'] = r['norm'], r['clip_coef'], r['skipped']
+        if not out:
+            raise RuntimeError('grad_report(): no gradient guard (train with --clip_grad_norm F or --skip_nonfinite)')
+        return out
+
     # ---- exponential moving average of the generator (--ema_decay; off = none of this runs) ---------------------------
     # The average lives in the generator's FusedAdam (optim.FusedAdam.attach_ema: the Adam kernel updates it in the pass
     # it already makes).  It is a deterministic function of the parameter trajectory: data-parallel ranks each keep their

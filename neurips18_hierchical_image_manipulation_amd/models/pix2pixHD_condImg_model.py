@@ -150,6 +150,7 @@ class Pix2PixHDModel_condImg(BaseModel):
             self.optimizer_G = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
             self.optimizer_D = FusedAdam(self.netD.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
             self._ema_attach(opt, opt.load_pretrain)
+            self._guard_attach(opt)                 # --clip_grad_norm / --skip_nonfinite: both optimizers
             self.reducer_G = self.reducer_D = None
             self.comm_timing = None
             self._g_chunked = False
@@ -834,7 +835,7 @@ class Pix2PixHDModel_condImg(BaseModel):
         self._ema_guard()
         self.sync()
         self.optimizer_G = FusedAdam(self.netG.parameters(), lr=self.opt.lr, betas=(self.opt.beta1, 0.999),
-                                     arena=self.optimizer_G.arena).adopt_ema(self.optimizer_G)
+                                     arena=self.optimizer_G.arena).adopt_ema(self.optimizer_G).adopt_guard(self.optimizer_G)
         print('------------ Now also finetuning global generator -----------')
 
     def update_learning_rate(self):

@@ -41,6 +41,56 @@ def ema_warm_count(decay):
     return lo
 
 
+GUARD_CHUNK = 16384      # floats per chunk of him_grad_stats (GS_CHUNK in csrc/him_optim.hip)
+
+
+def guard_tables(offsets, sizes, total, chunk=GUARD_CHUNK):
+    """The segment table handed to ``him_grad_stats`` and the chunk list its summation order is defined by.
+
+    ``seg``: one ``(begin, length)`` per parameter.  ``work``: ``(range, start, length)`` per chunk, in the order the
+    kernel numbers them: the arena is cut into the ranges gap 0, parameter 0, gap 1, ..., parameter N-1, tail gap (range
+    ``2 i + 1`` is parameter ``i``; gaps are the 256-byte padding and may be empty) and every range into chunks of
+    ``chunk`` floats counted from the range's own start.  The library derives the same list on the device from ``seg``
+    (the table lives in device memory); here it sizes the workspace check and documents the order."""
+    seg, work, at = [], [], 0
+
+    def cut(r, b, e):
+        for s in range(b, e, chunk):
+            work.append((r, s, min(chunk, e - s)))
+
+    for i, (o, n) in enumerate(zip(offsets, sizes)):
+        o, n = int(o), int(n)
+        if o < at or n < 0 or o + n > total:
+            raise ValueError('parameter %d: [%d, %d) is not a sorted, disjoint sub-range of [0, %d)' % (i, o, o + n, total))
+        seg.append((o, n))
+        cut(2 * i, at, o)
+        cut(2 * i + 1, o, o + n)
+        at = o + n
+    cut(2 * len(seg), at, int(total))
+    return seg, work
+
+
+class GradGuard(object):
+    """Device state of ``FusedAdam.attach_guard``: everything ``him_grad_stats`` writes and the guarded Adam kernel reads."""
+
+    def __init__(self, arena, max_norm, skip_nonfinite):
+        dev = arena.data.device
+        self.max_norm, self.skip_nonfinite = max_norm, skip_nonfinite
+        seg, work = guard_tables(arena.offsets, [p.numel() for p in arena.params], arena.total)
+        self.nseg, self.chunks = len(seg), len(work)
+        self.seg = torch.tensor(seg, dtype=torch.int64).reshape(-1, 2).to(dev)
+        self.seg_out = torch.zeros(self.nseg, 2, dtype=torch.float64, device=dev)
+        self.st = torch.zeros(8, dtype=torch.float64, device=dev)           # cumulative slots 4, 5: zeroed once, here
+        # clipping without the skip: the Adam kernel reads its flag (slot 1) from a second st whose slot 1 stays zero and
+        # whose slot 3 receives the coefficient by a one-element device copy after every stats pass
+        self.st_adam = self.st if skip_nonfinite else torch.zeros(8, dtype=torch.float64, device=dev)
+        self.ws_bytes = int(lib.him_grad_stats_ws(arena.total, self.nseg))
+        if self.ws_bytes < 32 * self.chunks:      # work-list entry + partial, 16 B each
+            raise RuntimeError('him_grad_stats_ws(%d, %d) = %d bytes cannot hold %d chunks'
+                               % (arena.total, self.nseg, self.ws_bytes, self.chunks))
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+
+
 class FlatArena(object):
     def __init__(self, params):
         self.params = [p for p in params]
@@ -107,6 +157,74 @@ class FusedAdam(object):
         self.ema_updates = 0          # EMA updates made so far (the ``t`` of ema_decay_at)
         self._ema_now = 0.0           # the decay of the step in flight: ONE value for all ranges of a step
         self._ema_swapped = False     # inside swap_ema() ... swap_ema(): the arena holds the averaged values
+        # gradient guard (attach_guard): off = nothing allocated, and _adam makes exactly the calls above
+        self.guard = None
+
+    # ---- gradient guard: global norm, clipping and the non-finite skip, decided on the device -----------------------
+    def attach_guard(self, max_norm=0.0, skip_nonfinite=True):
+        """From now on every ``step()`` first runs ``him_grad_stats`` over the whole gradient arena and then the guarded
+        Adam kernel, which reads the outcome from device memory -- nothing synchronises with the host.
+
+        ``max_norm`` > 0: global-norm clipping by the rule of ``torch.nn.utils.clip_grad_norm_``, applied to the gradient
+        as Adam reads it; the ``.grad`` buffers are NOT rewritten (unlike torch).  0 or inf: no clipping.
+        ``skip_nonfinite``: a step whose gradient holds an Inf or NaN stores nothing -- parameters, both moments and the
+        weight EMA keep their bits.  False: the statistics are still taken, but the kernel is handed a second ``st``
+        buffer whose non-finite slot stays zero (only the clip coefficient is copied into it, on the device).
+
+        DEVIATION from ``torch.cuda.amp.GradScaler``: the host cannot know the outcome without a synchronisation, so a
+        skipped step KEEPS its step number -- ``step_count`` and ``ema_updates`` count attempts, and the next step's bias
+        corrections are those of one step later; ``grad_report()['skipped']`` (slot 5 of ``st``) counts the skips.
+
+        Piecewise steps: the global norm needs every gradient, so with a guard ``step_range`` only records its range
+        and ``step()`` updates the whole arena -- bit-identical to a plain guarded ``step()``.
+
+        Data parallel: ``step()`` runs after the reducer has finished, on gradients every rank holds identically, and
+        the statistics are a deterministic function of them: the ranks decide alike without another collective."""
+        max_norm = float(max_norm)
+        if not max_norm >= 0.0:
+            raise ValueError('max_norm %r: a value >= 0 (0 = no clipping)' % max_norm)
+        if getattr(self, '_done', None) is not None:
+            raise RuntimeError('attach_guard inside an open piecewise step')
+        self.guard = GradGuard(self.arena, max_norm, bool(skip_nonfinite))
+        return self
+
+    def adopt_guard(self, other):
+        """Take over ``other``'s guard, counters included (an optimizer rebuilt over the same arena)."""
+        if other.guard is not None:
+            if other.arena is not self.arena:
+                raise ValueError('adopt_guard: the two optimizers walk different arenas')
+            self.guard = other.guard
+        return self
+
+    def _guard_stats(self):
+        a, gd = self.arena, self.guard
+        lib.him_grad_stats(a.grad.data_ptr(), a.total, gd.seg.data_ptr(), gd.nseg, gd.seg_out.data_ptr(), gd.st.data_ptr(),
+                           gd.max_norm, gd.ws.data_ptr(), gd.ws_bytes, _stream())
+        if gd.st_adam is not gd.st:
+            gd.st_adam[3:4].copy_(gd.st[3:4])
+
+    def grad_stats(self):
+        """``(st, norms)`` on the DEVICE, as the last ``step()`` left them: the 8 doubles of ``him_grad_stats`` and the
+        gradient norm of every parameter (arena order).  Reading them on the host synchronises; ``grad_report`` does."""
+        if self.guard is None:
+            raise RuntimeError('no gradient guard attached (attach_guard)')
+        return self.guard.st, self.guard.seg_out[:, 0].sqrt()
+
+    def grad_report(self, network=None):
+        """Host dict of the last step's statistics -- THE synchronising call, for print time only.  With ``network``:
+        ``per_param`` (norm by parameter name) and ``worst``, the name with the most non-finite elements, else the
+        largest norm."""
+        st, norms = self.grad_stats()
+        st = st.cpu().tolist()
+        out = dict(norm=st[2], clip_coef=st[3], nonfinite=int(st[1]), steps=int(st[4]), skipped=int(st[5]))
+        if network is not None:
+            by_id = {id(p): i for i, p in enumerate(self.arena.params)}
+            norms, bad = norms.cpu().tolist(), self.guard.seg_out[:, 1].cpu().tolist()
+            names = [(k, by_id[id(p)]) for k, p in network.named_parameters() if id(p) in by_id]
+            out['per_param'] = {k: norms[i] for k, i in names}
+            if names:
+                out['worst'] = max(names, key=lambda ki: (bad[ki[1]], norms[ki[1]]))[0]
+        return out
 
     # ---- exponential moving average of the arena, computed by the Adam kernel itself (him_adam_ema_step) ----
     def attach_ema(self, decay, ema=None, updates=0):
@@ -231,7 +349,12 @@ class FusedAdam(object):
             s, e = max(s, lo), min(e, hi)
             if s >= e:
                 continue
-            if self.ema is None:
+            if self.guard is not None:      # the kernel reads the skip flag and the clip coefficient from guard.st_adam
+                lib.him_adam_guarded_step(a.data.data_ptr() + 4 * s, a.grad.data_ptr() + 4 * s,
+                                          self.exp_avg.data_ptr() + 4 * s, self.exp_avg_sq.data_ptr() + 4 * s,
+                                          0 if self.ema is None else self.ema.data_ptr() + 4 * s, e - s, lr, b1, b2, eps,
+                                          self.step_count, self._ema_now, self.guard.st_adam.data_ptr(), _stream())
+            elif self.ema is None:
                 lib.him_adam_step(a.data.data_ptr() + 4 * s, a.grad.data_ptr() + 4 * s, self.exp_avg.data_ptr() + 4 * s,
                                   self.exp_avg_sq.data_ptr() + 4 * s, e - s, lr, b1, b2, eps, self.step_count, _stream())
             else:       # the same pass also averages [s, e): every element exactly once per step, as Adam visits it
@@ -256,6 +379,10 @@ class FusedAdam(object):
         if getattr(self, '_done', None) is None:
             raise RuntimeError('step_range outside begin_step() ... step()')
         self._check_live()
+        if self.guard is not None:
+            # the global norm needs EVERY gradient: the range is only recorded, step() updates the whole arena at once
+            self._done.append((lo, hi))
+            return
         self._adam(lo, hi)
         self._done.append((lo, hi))
         from .ops import refresh_panels
@@ -280,6 +407,12 @@ class FusedAdam(object):
             if at < a.total:
                 todo.append((at, a.total))
             self._done = None
+        if self.guard is not None:
+            # One statistics pass over the whole arena, then the guarded kernel over all of it (step_range has applied
+            # nothing).  Data parallel: the reducer has finished, every rank holds the same gradients and the statistics
+            # are a deterministic function of them, so the ranks take the same decision without another collective.
+            todo, done = [(0, a.total)], None
+            self._guard_stats()
         for lo, hi in todo:
             self._adam(lo, hi)
         # everything that reads the RAW parameters may start here; every cached weight panel carries its own event

@@ -79,6 +79,9 @@ BUILD_FLAGS = [('vgg_weights', str, ''), ('verbose', 'flag', False), ('color_noi
                # weight EMA of the generator: --ema_decay d > 0 averages it inside the Adam pass (0 = off, no buffer) and
                # save() adds <epoch>_net_G_ema.pth; --use_ema loads that file at test time
                ('ema_decay', float, 0.0), ('use_ema', 'flag', False),
+               # gradient guard of both optimizers (optim.FusedAdam.attach_guard): --clip_grad_norm F > 0 clips the global
+               # gradient norm of each network to F, --skip_nonfinite drops a step whose gradient holds an Inf or NaN
+               ('clip_grad_norm', float, 0.0), ('skip_nonfinite', 'flag', False),
                ('sn_D', 'flag', False)]             # spectral-norm convolutions in the multi-scale PatchGAN (sn_utils.py)   # loader: label ids as uint8 (the trainers widen them on the device)
 
 
@@ -86,6 +89,8 @@ BUILD_FLAGS = [('vgg_weights', str, ''), ('verbose', 'flag', False), ('color_noi
 # attributes with these defaults; ``parse`` also accepts ``--ema_decay d`` / ``--use_ema`` in the argument list (a
 # JointInference script may carry them) and takes them out before argparse sees the rest.
 EMA_ATTRS = (('ema_decay', float, 0.0), ('use_ema', 'flag', False))
+# the gradient-guard settings travel the same way
+GUARD_ATTRS = (('clip_grad_norm', float, 0.0), ('skip_nonfinite', 'flag', False))
 
 
 def _take_attr_flags(argv, attrs):
@@ -160,7 +165,7 @@ class BoxToMaskOptions(MaskToImageOptions):
     behaviour as the mask2image parser)."""
     isTrain = False
     tables = [BOX2MASK_BASE_FLAGS]
-    attrs = EMA_ATTRS
+    attrs = EMA_ATTRS + GUARD_ATTRS
 
 
 class BoxToMaskTrainOptions(BoxToMaskOptions):
