@@ -810,6 +810,62 @@ int him_label_instances(const void* cls, int cls_kind, int B, int H, int W, cons
                         int min_area, int base_id, int max_objects, int* inst_out, int* status, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Differentiable discriminator augmentation (Zhao et al., "Differentiable Augmentation for Data-Efficient GAN
+ * Training", NeurIPS 2020; the reference ships none): brightness -> saturation -> contrast -> translation with zero
+ * fill -> cutout, applied with ONE parameter row per sample to a dense (B,C,H,W) tensor, the concatenated discriminator
+ * input.  Channels [c0, c0+3) are the image; every other channel is condition and takes part in the geometric steps only.
+ *   table: int32 (B,8) on the device: [bits(b), bits(a), bits(k), ty, tx, cut_y0, cut_x0, policy_bits]; b, a, k are fp32
+ *          values stored as their bits.  policy_bits: HIM_AUG_COLOR | HIM_AUG_TRANSLATION | HIM_AUG_CUTOUT; a cleared
+ *          bit SKIPS that step (it is not run with neutral values), so a row with only geometric bits copies and zeroes.
+ *   policy: the steps this CALL may run; a row's effective bits are policy_bits & policy.  Without HIM_AUG_COLOR in
+ *          `policy` no channel is treated as image, c0 is not constrained and ws may be NULL.
+ *   ch, cw: the cutout's size, scalars of the call.
+ * Forward, output element (b,c,y,x): 0 if (y+ty, x+tx) lies outside the plane; 0 if (y,x) lies in
+ *   [cut_y0, cut_y0+ch) x [cut_x0, cut_x0+cw); else in[b,c,y+ty,x+tx], for the image channels of a colour row after the
+ *   colour map  v_c = in_c + b,  p = (v_0+v_1+v_2)/3,  s_c = (v_c - p) a + p,  m = mean_b + b,  o_c = (s_c - m) k + m,
+ *   with mean_b the mean of the sample's three image channels over the whole, untranslated plane (brightness and
+ *   saturation leave the per-sample mean at mean(x) + b, so one reduction of the INPUT serves the contrast step).
+ * Backward, the exact adjoint: g[b,c,y',x'] = dout[b,c,y'-ty,x'-tx] if that output position is in the plane and not
+ *   cut, else 0; condition channels dx = g; image channels of a colour row, with S_b = sum over c,y',x' of g and
+ *   N = 3 H W:  ds_c = k g_c + (1-k) S_b/N,  dx_c = a ds_c + (1-a)(ds_0+ds_1+ds_2)/3.
+ *   Only channels [g0, g0+gn) are computed: dx is (B,gn,H,W), channel c of the input at channel c - g0.
+ * Any table content is legal: shifts of +-H / +-W and beyond give zeros, a rectangle may be empty, hang over an edge or
+ *   cover the plane; the kernels clamp both, no content moves an address outside the buffers.
+ * ws: him_diffaug_ws(B,H,W) bytes, needed with HIM_AUG_COLOR.  After the call the first B doubles at ws rounded up to 8
+ *   bytes hold the per-sample sums (forward: of the image channels of x; backward: S_b; 0 for a row without the colour
+ *   bit).  Both sums are accumulated in double without atomics in a fixed tree over chunks of 16384 floats counted from
+ *   the sample's first image element: a pure function of the inputs, independent of the grid (him_grad_stats' rule).
+ * Each pass is one read and one write of the tensor (16 bytes per lane at any 4-byte alignment of base, row and shift)
+ *   plus, with HIM_AUG_COLOR, one more read of the image channels and two small launches.
+ * HIM_E_INVALID before any launch: a NULL x / table / y (or ws with HIM_AUG_COLOR), a negative size, unknown policy
+ *   bits, c0 + 3 > C with HIM_AUG_COLOR in `policy`, [g0, g0+gn) outside [0, C), H * W > 2^29, or a workspace below the
+ *   query.  Asynchronous, no allocation.
+ *
+ * him_diffaug_draw fills the table on the device; nothing is staged on the host, nothing synchronises.
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31  (the splitmix64
+ *           finaliser), all arithmetic modulo 2^64, G = 0x9E3779B97F4A7C15.
+ *   key = mix(mix(mix(seed + G) + step + G) + (sample0 + b) + G);   z_i = mix(key + (i + 1) G), i = 0..6.
+ *   uniform u_i = (z_i >> 40) 2^-24;   integer in [lo, hi]: lo + (((z_i >> 32) (hi - lo + 1)) >> 32).
+ *   b = u_0 - 0.5,  a = 2 u_1,  k = u_2 + 0.5  (each rounded to fp32 once);
+ *   ty in [-sy, sy] from z_3 with sy = floor(H rt + 0.5), tx in [-sx, sx] from z_4 with sx = floor(W rt + 0.5);
+ *   ch = floor(H rc + 0.5), oy in [0, H - (ch mod 2)] from z_5, cut_y0 = oy - floor(ch / 2); cw, z_6, cut_x0 likewise
+ *   (the products in double).  DiffAugment's defaults are rt = 0.125, rc = 0.5.
+ *   A step missing from `policy` leaves its neutral values (b 0, a 1, k 1; ty tx 0; cut_y0 cut_x0 0) and its bit clear;
+ *   *ch and *cw (host) receive the cutout size, 0 without HIM_AUG_CUTOUT.
+ *   HIM_E_INVALID: NULL pointer, B < 0, H or W outside 1..2^20, unknown policy bits, a ratio negative, NaN or > 1024.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_AUG_COLOR 1
+#define HIM_AUG_TRANSLATION 2
+#define HIM_AUG_CUTOUT 4
+size_t him_diffaug_ws(int B, int H, int W);
+int him_diffaug_fwd(const float* x, const int* table, float* y, int B, int C, int c0, int H, int W, int ch, int cw,
+                    int policy, void* ws, size_t ws_bytes, void* stream);
+int him_diffaug_bwd(const float* dout, const int* table, float* dx, int B, int C, int c0, int H, int W, int ch, int cw,
+                    int policy, int g0, int gn, void* ws, size_t ws_bytes, void* stream);
+int him_diffaug_draw(int* table, int B, int H, int W, long long seed, long long step, long long sample0, int policy,
+                     double ratio_translation, double ratio_cutout, int* ch, int* cw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,11 @@ _SIGS = {
     'him_grad_stats': (c_int, [P, c_size_t, P, c_int, P, P, c_double, P, c_size_t, P]),
     'him_adam_guarded_step': (c_int, [P, P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, c_double, P,
                                       P]),
+    'him_diffaug_ws': (c_size_t, [c_int, c_int, c_int]),
+    'him_diffaug_fwd': (c_int, [P, P, P] + [c_int] * 8 + [P, c_size_t, P]),
+    'him_diffaug_bwd': (c_int, [P, P, P] + [c_int] * 10 + [P, c_size_t, P]),
+    'him_diffaug_draw': (c_int, [P, c_int, c_int, c_int, C.c_longlong, C.c_longlong, C.c_longlong, c_int, c_double,
+                                 c_double, C.POINTER(c_int), C.POINTER(c_int), P]),
     'him_fill': (c_int, [P, c_size_t, c_float, P]),
     'him_scale': (c_int, [P, c_size_t, c_float, P]),
     'him_sn_ws': (c_size_t, [c_int, c_int]),

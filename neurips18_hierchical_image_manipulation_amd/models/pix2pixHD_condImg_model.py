@@ -13,7 +13,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .. import ops, synth
+from .. import augment, ops, synth
 from ..config import SCHED
 from ..nn import frozen_params
 from ..optim import FusedAdam
@@ -99,6 +99,21 @@ class Pix2PixHDModel_condImg(BaseModel):
                 elif isinstance(m, _HimDeconv2d):
                     m.weight._him_wgrad_alt = 'head'     # config.SCHED.g_head_wgrad_alt
 
+        # differentiable discriminator augmentation (--diffaug): training only; 0 = off, today's path
+        self._diffaug_bits = 0
+        self._diffaug_table = None
+        self._diffaug_size = (0, 0)
+        self._diffaug_step = 0          # steps drawn since construction; NOT checkpointed (a resumed run starts at 0 again)
+        if self.isTrain:
+            self._diffaug_bits = augment.parse_policy(getattr(opt, 'diffaug', ''))
+            if self._diffaug_bits:
+                if (self._diffaug_bits & augment.COLOR) and opt.output_nc != 3:
+                    raise ValueError('--diffaug color needs a 3-channel image (output_nc %d)' % opt.output_nc)
+                self._diffaug_ratios = (float(getattr(opt, 'diffaug_translation', 0.125)),
+                                        float(getattr(opt, 'diffaug_cutout', 0.5)))
+                if not all(0.0 <= r <= 1024.0 for r in self._diffaug_ratios):
+                    raise ValueError('--diffaug_translation / --diffaug_cutout must lie in [0, 1024]')
+                self._diffaug_seed = int(getattr(opt, 'diffaug_seed', 0)) + int(os.environ.get('RANK', '0'))
         if self.isTrain:
             self.no_imgCond = opt.no_imgCond
             self.mask_gan_input = opt.mask_gan_input
@@ -232,7 +247,8 @@ class Pix2PixHDModel_condImg(BaseModel):
         """True when the discriminators get (condition, image) as an ``ops.CondImage`` pair instead of their concatenation:
         no mask on the input, no image pool (it stores concatenated tensors), a condition at all."""
         ctx_only = self.opt.netG == 'global_twostream' and self.opt.which_encoder == 'ctx'
-        return SCHED.d_split_input and not ctx_only and not self.mask_gan_input and self.opt.pool_size == 0
+        return (SCHED.d_split_input and not ctx_only and not self.mask_gan_input and self.opt.pool_size == 0
+                and not self._diffaug_bits)     # the augmentation acts on the dense concatenated input
 
     def _d_input(self, cond, image, mask):
         if self.opt.netG == 'global_twostream' and self.opt.which_encoder == 'ctx':
@@ -241,11 +257,34 @@ class Pix2PixHDModel_condImg(BaseModel):
             return ops.CondImage(cond, image)       # condition and image kept apart (see ops.CondImage)
         return ops.cat_channels([cond, image], mask if self.mask_gan_input else None, 1)
 
+    def _d_augment(self, x):
+        """--diffaug: the step's ONE table applied to a discriminator input (real and fake alike: feature matching compares
+        their PatchGAN features position by position).  Behind the mask multiply and the image pool, which stores
+        un-augmented tensors.  The image is the last ``output_nc`` channels.  Identity with the policy off."""
+        if not self._diffaug_bits or self._diffaug_table is None:
+            return x
+        ch, cw = self._diffaug_size
+        return ops.diff_augment(x, self._diffaug_table, ch, cw, x.shape[1] - self.opt.output_nc, self._diffaug_bits)
+
+    def _diffaug_draw(self, B, H, W):
+        """The step's parameter table, drawn on the device on the CURRENT stream from (seed + rank, step counter, sample)."""
+        rt, rc = self._diffaug_ratios
+        self._diffaug_table, ch, cw = ops.diffaug_draw(B, H, W, self._diffaug_seed, self._diffaug_step, 0,
+                                                       self._diffaug_bits, rt, rc, device=self.device)
+        self._diffaug_size = (ch, cw)
+        self._diffaug_step += 1
+        return self._diffaug_table
+
+    def diffaug_table(self):
+        """The int32 (B, 8) parameter table of the last training step on the device (None before the first step / with the
+        policy off); ``augment.draw(B, H, W, seed + rank, step, 0, bits, ...)`` gives the same rows on the host."""
+        return self._diffaug_table
+
     def discriminate(self, input_label, test_image, mask, use_pool=False):
         x = self._d_input(input_label, test_image.detach(), mask)
         if use_pool:
             x = self.fake_pool.query(x)
-        return self.netD.forward(x)
+        return self.netD.forward(self._d_augment(x))
 
     def _real_branch_ahead(self, netD_cond, real_image, mask_cond, inputs_ready=None):
         """D(real) + LSGAN loss and VGG(real) on the side stream (None when disabled).  ``inputs_ready``: event recorded
@@ -287,6 +326,8 @@ class Pix2PixHDModel_condImg(BaseModel):
             t.record_stream(main)
         for t in (netD_cond, real_image, mask_cond) + tuple(getattr(netD_cond, '_him_pyramid', ())):
             t.record_stream(side)
+        if self._diffaug_bits and self._diffaug_table is not None:
+            self._diffaug_table.record_stream(side)
         return out
 
     def _generate(self, buf, input_mask, cond_image, mask_in):
@@ -321,6 +362,11 @@ class Pix2PixHDModel_condImg(BaseModel):
             if self._d_split():
                 # the pooled condition of the PatchGAN scales: once per step, before the streams fork (every pass reads it)
                 ops.cond_pyramid(netD_cond, opt.num_D, prefill=2 if self.isTrain else 0, image_channels=opt.output_nc)
+            aug_table = None
+            if self.isTrain and self._diffaug_bits:
+                # ONE table per step, in front of the event every stream of the step waits for (the real-image branch
+                # is forked behind it)
+                aug_table = self._diffaug_draw(real_image.shape[0], real_image.shape[2], real_image.shape[3])
             inputs_ready = torch.cuda.Event()
             inputs_ready.record(torch.cuda.current_stream(self.device))
         if enc_side is not None:
@@ -329,6 +375,8 @@ class Pix2PixHDModel_condImg(BaseModel):
                     getattr(netD_cond, '_him_pyramid', ())):
                 if torch.is_tensor(t) or isinstance(t, ops.LabelCond):
                     t.record_stream(main)        # allocated on the real-image stream, read on the main one
+            if aug_table is not None:
+                aug_table.record_stream(main)
 
         # Everything that depends only on the REAL image (its discriminator pass and its VGG features) is independent
         # of the generator: it runs on a side stream next to the generator forward and fills the matrix pipe where the
@@ -382,8 +430,8 @@ class Pix2PixHDModel_condImg(BaseModel):
         share = opt.pool_size == 0 and self._share_fake_pass and not self._d_stateful()
         if share:
             self._fake_gate = {'open': True}
-            pred_fake = self.netD.forward(self._d_input(netD_cond, ops.grad_switch(fake_image, self._fake_gate),
-                                                        mask_cond))
+            pred_fake = self.netD.forward(self._d_augment(self._d_input(
+                netD_cond, ops.grad_switch(fake_image, self._fake_gate), mask_cond)))
             pred_fake_pool = pred_fake
         else:
             self._fake_gate = None
@@ -396,7 +444,7 @@ class Pix2PixHDModel_condImg(BaseModel):
             loss_D_real = self.criterionGAN(pred_real, True)
         if not share:
             with frozen_params():
-                pred_fake = self.netD.forward(self._d_input(netD_cond, fake_image, mask_cond))
+                pred_fake = self.netD.forward(self._d_augment(self._d_input(netD_cond, fake_image, mask_cond)))
         loss_G_GAN = self.criterionGAN(pred_fake, True)
 
         loss_G_GAN_Feat = None

@@ -1691,6 +1691,79 @@ def mul_mask(x, mask):
     return _CatMask.apply(mask, 1, x)
 
 
+class _DiffAugment(torch.autograd.Function):
+    """him_diffaug_fwd / him_diffaug_bwd (include/him.h): colour -> translation -> cutout with one table row per sample."""
+
+    @staticmethod
+    def forward(ctx, x, table, ch, cw, c0, policy):
+        ctx.set_materialize_grads(False)   # an undefined gradient stays None: backward returns early
+        x = x.contiguous()
+        _chk(x)
+        B, C, H, W = x.shape
+        _chk_table(table, B)
+        y = torch.empty_like(x)
+        nb = int(lib.him_diffaug_ws(B, H, W)) if policy & 1 else 0
+        ws = _ws(nb, x) if nb else None
+        lib.him_diffaug_fwd(_p(x), table.data_ptr(), _p(y), B, C, c0, H, W, ch, cw, policy, _p(ws), nb, _stream())
+        ctx.table, ctx.args = table, (B, C, c0, H, W, ch, cw, policy)
+        ctx.gslice = getattr(x, '_him_grad_slice', None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dout):
+        if dout is None:
+            return (None,) * 6
+        B, C, c0, H, W, ch, cw, policy = ctx.args
+        dout = dout.contiguous()
+        nb = int(lib.him_diffaug_ws(B, H, W)) if policy & 1 else 0
+        ws = _ws(nb, dout) if nb else None
+        st = _stream()
+        gs = ctx.gslice
+        if gs is not None and gs[1] < C:
+            # only channels [g0, g0+n) of the input can use a gradient (the image behind the condition): those alone are
+            # computed, zeros elsewhere -- what such an input receives from ``_Conv2d.backward`` too
+            g0, n = gs
+            dxs = torch.empty((B, n, H, W), dtype=torch.float32, device=dout.device)
+            lib.him_diffaug_bwd(_p(dout), ctx.table.data_ptr(), _p(dxs), B, C, c0, H, W, ch, cw, policy, g0, n, _p(ws), nb, st)
+            dx = torch.zeros_like(dout)
+            lib.him_copy_channels(_p(dxs), n, 0, _p(dx), C, g0, n, B, H * W, 0, 0, 0, st)
+        else:
+            dx = torch.empty_like(dout)
+            lib.him_diffaug_bwd(_p(dout), ctx.table.data_ptr(), _p(dx), B, C, c0, H, W, ch, cw, policy, 0, C, _p(ws), nb, st)
+        return dx, None, None, None, None, None
+
+
+def _chk_table(table, B):
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous()
+            and tuple(table.shape) == (B, 8)):
+        raise HimError('diff_augment: the parameter table must be a contiguous int32 (B, 8) GPU tensor')
+
+
+def diff_augment(x, table, ch, cw, c0, policy=7):
+    """DiffAugment of the dense discriminator input ``x`` (B,C,H,W): channels [c0, c0+3) are the image, the others only
+    move with it.  ``table``: int32 (B,8) from ``diffaug_draw``; ``policy`` masks the rows' own bits."""
+    if isinstance(x, (LabelCond, CondImage)):
+        raise HimError('diff_augment works on the dense concatenated discriminator input')
+    y = _DiffAugment.apply(x, table, int(ch), int(cw), int(c0), int(policy) & 7)
+    gs = getattr(x, '_him_grad_slice', None)
+    if gs is not None:
+        y._him_grad_slice = gs      # channel-wise op: the same slice is the only one that needs a gradient
+    return y
+
+
+def diffaug_draw(B, H, W, seed, step, sample0, policy, ratio_translation=0.125, ratio_cutout=0.5, device=None, out=None):
+    """-> (table, ch, cw): the int32 (B,8) parameter table drawn ON THE DEVICE on the current stream (no host copy, no
+    synchronisation) and the cutout size of the call; ``augment.draw`` gives the same integers on the host."""
+    table = out if out is not None else torch.empty((int(B), 8), dtype=torch.int32,
+                                                     device=device if device is not None else torch.device('cuda'))
+    _chk_table(table, int(B))
+    ch, cw = ctypes.c_int(0), ctypes.c_int(0)
+    with torch.cuda.device(table.device):
+        lib.him_diffaug_draw(table.data_ptr(), int(B), int(H), int(W), int(seed), int(step), int(sample0), int(policy),
+                             float(ratio_translation), float(ratio_cutout), ctypes.byref(ch), ctypes.byref(cw), _stream())
+    return table, ch.value, cw.value
+
+
 class _Blend(torch.autograd.Function):
     """out = (1-m) * a[:, a0:a0+C] + m * b    (m: (B,1,H,W))."""
 

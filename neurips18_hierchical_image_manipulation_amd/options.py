@@ -85,6 +85,15 @@ BUILD_FLAGS = [('vgg_weights', str, ''), ('verbose', 'flag', False), ('color_noi
                ('sn_D', 'flag', False)]             # spectral-norm convolutions in the multi-scale PatchGAN (sn_utils.py)   # loader: label ids as uint8 (the trainers widen them on the device)
 
 
+# Differentiable discriminator augmentation (models/pix2pixHD_condImg_model.py), next to --ema_decay but for
+# the mask2image TRAINING parser only (``MaskToImageTrainOptions.extra_tables``): the test-time parsers build no
+# discriminator and the box2mask trainer has no augmentation.  --diffaug '' (off) or a comma list out of
+# color,translation,cutout (anything else raises when the model is built); --diffaug_seed; the largest shift and the cutout
+# size as fractions of the plane (DiffAugment's 0.125 and 0.5).
+DIFFAUG_FLAGS = [('diffaug', str, ''), ('diffaug_seed', int, 0), ('diffaug_translation', float, 0.125),
+                 ('diffaug_cutout', float, 0.5)]
+
+
 # The box2mask parsers keep exactly the reference's argparse tables, so the two EMA settings travel there as ``opt``
 # attributes with these defaults; ``parse`` also accepts ``--ema_decay d`` / ``--use_ema`` in the argument list (a
 # JointInference script may carry them) and takes them out before argparse sees the rest.
@@ -114,6 +123,7 @@ def _take_attr_flags(argv, attrs):
 class MaskToImageOptions(object):
     isTrain = False
     tables = [BASE_FLAGS, BUILD_FLAGS]
+    extra_tables = []       # flags of ONE parser that are no part of the tables shared with the reference's parsers
     attrs = ()
 
     def __init__(self):
@@ -121,7 +131,7 @@ class MaskToImageOptions(object):
         self.initialized = False
 
     def initialize(self):
-        for table in self.tables:
+        for table in list(self.tables) + list(self.extra_tables):
             for name, typ, default in table:
                 if typ == 'flag':
                     self.parser.add_argument('--' + name, action='store_true')
@@ -152,6 +162,7 @@ class MaskToImageOptions(object):
 class MaskToImageTrainOptions(MaskToImageOptions):
     isTrain = True
     tables = [BASE_FLAGS, TRAIN_FLAGS, BUILD_FLAGS]
+    extra_tables = [DIFFAUG_FLAGS]
 
 
 class MaskToImageTestOptions(MaskToImageOptions):
@@ -187,7 +198,7 @@ def complete(opt):
         # create_model rejects (models/models.py:16-17): every shipped script passes --model.  A partial dict / Namespace
         # handed to this function means the hot-path trainer.
         opt.model = 'pix2pixHD_condImg'
-    for table in (BASE_FLAGS, TRAIN_FLAGS, BUILD_FLAGS):
+    for table in (BASE_FLAGS, TRAIN_FLAGS, BUILD_FLAGS, DIFFAUG_FLAGS):
         for name, typ, default in table:
             if not hasattr(opt, name):
                 setattr(opt, name, default)
