@@ -866,6 +866,77 @@ int him_diffaug_bwd(const float* dout, const int* table, float* dx, int B, int C
 int him_diffaug_draw(int* table, int B, int H, int W, long long seed, long long step, long long sample0, int policy,
                      double ratio_translation, double ratio_cutout, int* ch, int* cw, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Distance transform and boundary metrics (the reference ships none): the exact Euclidean distance transform of label
+ * planes, and on it the contour measures of a predicted layout or object mask against the ground truth.  Integer work,
+ * everything on `stream`, no host synchronisation, results bit-identical from run to run.
+ *
+ * him_edt: K independent jobs over the B planes of src; per job the squared distance from every pixel to the nearest
+ * SEED pixel of the job's plane and, optionally, that seed's index (the feature transform).
+ *   src:    (B,H,W), kind 0 uint8 / 1 int32 / 2 int64 / 3 fp32 holding integral ids (him_confusion's kinds); any base
+ *           aligned to the element, any width; never written.
+ *   jobs:   int32 (K,3) on the device, row k = [plane b, value v, rule]:
+ *             HIM_EDT_NONZERO       seeds = pixels with src != 0;
+ *             HIM_EDT_EQUALS        seeds = pixels with src == v;
+ *             HIM_EDT_BOUNDARY_OF   seeds = pixels with src == v that have a 4-neighbour INSIDE the plane with
+ *                                   src != v: the inner boundary of class v (the image border alone makes none);
+ *             HIM_EDT_ANY_BOUNDARY  seeds = pixels with a 4-neighbour inside the plane holding another value.
+ *   dist2:  int32 (K,H,W): min over seeds of (x - x')^2 + (y - y')^2, exact; HIM_EDT_NONE on every pixel of a job
+ *           without a seed.
+ *   nearest: NULL, or int32 (K,H,W): y' * W + x' of a nearest seed; among equidistant seeds the smallest index (the
+ *           smallest y', then the smallest x'); -1 where there is no seed.
+ *   status: int32 (K,2) written by the device: [k][0] = the job's seed count, [k][1] = flag bits; HIM_EDT_BAD_JOB marks
+ *           a job whose plane is outside 0..B-1 or whose rule is unknown: it writes HIM_EDT_NONE / -1, counts 0 seeds
+ *           and reads no plane.
+ *   ws:     him_edt_workspace(K, H, W) bytes (an int16 per pixel and job, rounded up to 16), 2-byte aligned; every
+ *           cell that is read is written by the call first.
+ *   Limits, refused with HIM_E_INVALID before any launch: B < 1, H or W outside 1..16384 (so dx^2 + dy^2 < 2^30 fits
+ *   an int32), K < 1, K * H * W > 2^40, a NULL src / jobs / dist2 / status / ws, an unknown kind, a pointer not aligned
+ *   to its element; HIM_E_WORKSPACE for a workspace below the query (which returns 0 for a refused shape).
+ *   Kernel layout, three launches.  Status: zero counts, job flags.  Row pass, a 256-thread workgroup per (row, job):
+ *   a prefix maximum of "x if seed else -1" walking right and a suffix minimum walking left (wave shuffles, a carry
+ *   between steps of 256 columns) give the nearest seed column of the row, the LEFT one on a tie, stored as int16;
+ *   seeds are counted with integer atomics.  Column pass, a workgroup per (64 columns x 32 rows, job), lane = column,
+ *   8 rows per thread: the row-pass columns are staged in LDS 64 rows at a time as (x - x')^2 and each thread minimises
+ *   (x - x')^2 + (y - y')^2, first over the chunk of its tile and upwards in decreasing y' with <=, then downwards in
+ *   increasing y' with <, so the smallest y' keeps a tie; a sweep stops once the chunk's row gap squared exceeds every
+ *   thread's current distance (a workgroup vote), so the work follows the distances, bounded by H.  A job without a seed
+ *   is answered from its count.  Integer arithmetic only, no cooperative launch, no workgroup waits for another.
+ *
+ * him_boundary_stats: one direction of a boundary comparison.  Job k has the seeds P_k of src under jobs[k] (as above);
+ * dist2 (K,H,W) holds the distances to the OTHER map's boundary (a him_edt result over the other map, same job table).
+ *   counts: int64 (K,4): [n_seed = |P_k|, n_matched = |{p : dist2 <= tol2}|, max_d2 over the reachable seeds (-1: none),
+ *           n_unreachable = |{p : dist2 == HIM_EDT_NONE}|]; unreachable seeds enter neither max_d2 nor the sum.
+ *   sumd:   double (K): sum over the reachable seeds of sqrt((double)dist2).  Each workgroup (16 rows of a job) writes its
+ *           partial to its own workspace slot, a second launch adds a job's slots in a fixed order: no floating-point
+ *           atomics, identical bits from run to run.
+ *   tol2 >= 0.  ws: him_boundary_stats_workspace(K, H, W) bytes, 8-byte aligned, written before it is read.  A
+ *   HIM_EDT_BAD_JOB row gives [0, 0, -1, 0] and 0.0.  Limits and refusals as him_edt.
+ * The measures util/metrics.py builds from the two directions, per sample and class c with dP / dG the
+ * HIM_EDT_BOUNDARY_OF c sets of prediction and ground truth and tol2 = floor(tolerance^2):
+ *   precision = |{p in dP : d2(p, dG) <= tol2}| / |dP|, recall its mirror image, f1 = 2 P R / (P + R) (0 when P + R = 0);
+ *   assd = (sum over dP of d(p, dG) + sum over dG of d(g, dP)) / (|dP| + |dG|);  hausdorff = sqrt(max of both max_d2);
+ *   both boundaries empty: all five nan; exactly one empty: precision = recall = f1 = 0, assd and hausdorff nan.
+ *   The band of radius r around the class boundaries of a map: dist2 <= floor(r^2) under HIM_EDT_ANY_BOUNDARY; a
+ *   confusion matrix restricted to it (him_confusion's mask) gives the "trimap" IoU.
+ *
+ * him_label_ids: fp32 scores (pred_kind 4, (B,C,H,W): the channel of the maximum, the lowest on a tie) or probabilities
+ * (pred_kind 5, C = 1: p > 0.5) to int32 ids (B,H,W), him_confusion's rules, so that predictions enter the two calls above.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_EDT_NONZERO 0
+#define HIM_EDT_EQUALS 1
+#define HIM_EDT_BOUNDARY_OF 2
+#define HIM_EDT_ANY_BOUNDARY 3
+#define HIM_EDT_NONE 2147483647
+#define HIM_EDT_BAD_JOB 1
+size_t him_edt_workspace(int K, int H, int W);
+int him_edt(const void* src, int kind, int B, int H, int W, const int* jobs, int K, int* dist2, int* nearest, int* status,
+            void* ws, size_t ws_bytes, void* stream);
+size_t him_boundary_stats_workspace(int K, int H, int W);
+int him_boundary_stats(const void* src, int kind, int B, int H, int W, const int* jobs, int K, const int* dist2, int tol2,
+                       long long* counts, double* sumd, void* ws, size_t ws_bytes, void* stream);
+int him_label_ids(const float* src, int pred_kind, int B, int C, int H, int W, int* ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,11 @@ _SIGS = {
                               c_size_t, P]),
     'him_label_instances_workspace': (c_size_t, [c_int, c_int, c_int]),
     'him_label_instances': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    'him_edt_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'him_edt': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, c_size_t, P]),
+    'him_boundary_stats_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'him_boundary_stats': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, c_size_t, P]),
+    'him_label_ids': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

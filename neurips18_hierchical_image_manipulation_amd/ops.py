@@ -2781,3 +2781,120 @@ def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, 
                           1 if per_sample else 0, 0 if out is None else 1, _p(counts), _p(status), _p(ws),
                           ws.numel() * 8, _stream())
     return counts, status
+
+
+# -- distance transform and boundary statistics (include/him.h "Distance transform and boundary metrics") --------------
+_EDT_WS = {}            # (K, H, W, device index) -> workspace of him_edt
+_BSTAT_WS = {}          # (K, H, W, device index) -> workspace of him_boundary_stats
+EDT_RULES = {'nonzero': 0, 'equals': 1, 'boundary_of': 2, 'any_boundary': 3}
+EDT_NONE, EDT_BAD_JOB = 2 ** 31 - 1, 1
+
+
+def _edt_planes(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('%s: src must be a device tensor' % what)
+    if t.dtype not in _PRED_KINDS:
+        raise ValueError('%s: src is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in _PRED_KINDS)))
+    if t.dim() == 2:
+        t = t[None]
+    elif t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or 0 in t.shape or max(t.shape[1:]) > 16384:
+        raise ValueError('%s: src must be (B, H, W), (B, 1, H, W) or (H, W) with H, W <= 16384, got %s'
+                         % (what, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def _edt_jobs(jobs, device, what):
+    if not torch.is_tensor(jobs) or not jobs.is_cuda or jobs.dtype != torch.int32 or jobs.dim() != 2 \
+            or jobs.shape[1] != 3 or jobs.shape[0] < 1 or jobs.device != device:
+        raise ValueError('%s: jobs must be a (K >= 1, 3) int32 tensor on the device of src' % what)
+    return jobs.contiguous()
+
+
+def edt_jobs(B, values, rule, device):
+    """The (B * len(values), 3) int32 job table [plane, value, rule] on ``device``, plane-major, built by device ops."""
+    rule = EDT_RULES[rule] if isinstance(rule, str) else int(rule)
+    n = len(values)
+    with torch.cuda.device(device):
+        k = torch.arange(B * n, dtype=torch.int32, device=device)
+        plane = torch.div(k, n, rounding_mode='floor')
+        if list(values) == list(range(values[0], values[0] + n)):
+            value = k - plane * n + int(values[0])
+        else:
+            value = torch.tensor(list(values), dtype=torch.int32).to(device)[(k - plane * n).long()]
+        return torch.stack([plane, value, torch.full_like(k, rule)], 1).contiguous()
+
+
+def distance_transform(src, jobs=None, value=None, rule='nonzero', want_nearest=False):
+    """``(dist2, nearest or None, status)`` on the device: for each job the exact squared Euclidean distance (int32,
+    (K, H, W)) from every pixel to the nearest seed of the job's plane, the seed's index ``y * W + x`` (the smallest among
+    equidistant ones; -1 without a seed) and the (K, 2) record [seed count, flag bits].  ``src``: uint8 / int32 / int64 /
+    integral fp32 ids, (B, H, W).  ``jobs``: a (K, 3) int32 device table [plane, value, rule number]; None runs one job
+    per plane with ``rule`` in ``EDT_RULES`` and ``value``.  ``EDT_NONE`` marks a job without a seed.  Current stream,
+    no host synchronisation, no autograd.  The workspace is cached per (K, H, W) and device: calls of one shape must be
+    queued on one stream at a time."""
+    src = _edt_planes(src, 'distance_transform')
+    B, H, W = src.shape
+    if jobs is None:
+        if rule not in EDT_RULES:
+            raise ValueError('distance_transform: rule %r (one of %s)' % (rule, ', '.join(EDT_RULES)))
+        jobs = edt_jobs(B, [0 if value is None else int(value)], rule, src.device)
+    jobs = _edt_jobs(jobs, src.device, 'distance_transform')
+    K = jobs.shape[0]
+    with torch.cuda.device(src.device):
+        key = (K, H, W, torch.cuda.current_device())
+        ws = _EDT_WS.get(key)
+        if ws is None:
+            ws = _EDT_WS[key] = torch.empty(max(int(lib.him_edt_workspace(K, H, W)) // 2, 1), dtype=torch.int16,
+                                            device=src.device)
+        dist2 = torch.empty((K, H, W), dtype=torch.int32, device=src.device)
+        nearest = torch.empty((K, H, W), dtype=torch.int32, device=src.device) if want_nearest else None
+        status = torch.empty((K, 2), dtype=torch.int32, device=src.device)
+        lib.him_edt(_p(src), _PRED_KINDS[src.dtype], B, H, W, _p(jobs), K, _p(dist2), _p(nearest), _p(status), _p(ws),
+                    ws.numel() * 2, _stream())
+    return dist2, nearest, status
+
+
+def boundary_stats(src, jobs, dist2, tol2):
+    """``(counts, sumd)`` on the device: per job over its seeds of ``src``, int64 (K, 4) [seeds, seeds with
+    ``dist2 <= tol2``, the largest reachable ``dist2`` (-1: none), seeds with ``dist2 == EDT_NONE``] and the float64 (K,)
+    sum of ``sqrt(dist2)`` over the reachable seeds, added in a fixed order.  ``dist2``: the (K, H, W) result of
+    ``distance_transform`` over the other map with the same job table.  Current stream, no host synchronisation."""
+    src = _edt_planes(src, 'boundary_stats')
+    B, H, W = src.shape
+    jobs = _edt_jobs(jobs, src.device, 'boundary_stats')
+    K = jobs.shape[0]
+    if not torch.is_tensor(dist2) or dist2.dtype != torch.int32 or tuple(dist2.shape) != (K, H, W) \
+            or dist2.device != src.device:
+        raise ValueError('boundary_stats: dist2 must be a (%d, %d, %d) int32 tensor on the device of src' % (K, H, W))
+    tol2 = int(tol2)
+    if tol2 < 0:
+        raise ValueError('boundary_stats: tol2 must not be negative, got %d' % tol2)
+    dist2 = dist2.contiguous()
+    with torch.cuda.device(src.device):
+        key = (K, H, W, torch.cuda.current_device())
+        ws = _BSTAT_WS.get(key)
+        if ws is None:
+            ws = _BSTAT_WS[key] = torch.empty(max(int(lib.him_boundary_stats_workspace(K, H, W)) // 8, 1),
+                                              dtype=torch.int64, device=src.device)
+        counts = torch.empty((K, 4), dtype=torch.int64, device=src.device)
+        sumd = torch.empty(K, dtype=torch.float64, device=src.device)
+        lib.him_boundary_stats(_p(src), _PRED_KINDS[src.dtype], B, H, W, _p(jobs), K, _p(dist2), tol2, _p(counts),
+                               _p(sumd), _p(ws), ws.numel() * 8, _stream())
+    return counts, sumd
+
+
+def label_ids(pred, pred_kind):
+    """int32 ids (B, H, W) on the device of fp32 scores (B, C, H, W) (``pred_kind='scores'``: the channel of the maximum,
+    the lowest on a tie) or probabilities (B, 1, H, W) (``'prob'``: p > 0.5), the rules of ``confusion``."""
+    if pred_kind not in ('scores', 'prob'):
+        raise ValueError("label_ids: pred_kind %r ('scores' or 'prob')" % (pred_kind,))
+    pred = _label_planes(pred, 'pred', (torch.float32,), scores=True)
+    B, C, H, W = pred.shape
+    if pred_kind == 'prob' and C != 1:
+        raise ValueError('label_ids: probability planes have one channel, got %s' % (tuple(pred.shape),))
+    with torch.cuda.device(pred.device):
+        ids = torch.empty((B, H, W), dtype=torch.int32, device=pred.device)
+        lib.him_label_ids(_p(pred), 4 if pred_kind == 'scores' else 5, B, C, H, W, _p(ids), _stream())
+    return ids

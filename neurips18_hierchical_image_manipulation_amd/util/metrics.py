@@ -1,6 +1,8 @@
 """Evaluation metrics on the device: SSIM / PSNR / L1 of a generated image against the real one (inside the edited box),
-pixel accuracy and IoU of a predicted layout, IoU of a generated object mask.  The reference ships no metric code; the
-definitions are those of include/him.h "Evaluation metrics".  Every function queues device work on the current stream
+pixel accuracy and IoU of a predicted layout, IoU of a generated object mask, and the contour measures of both (boundary
+F-score, average symmetric surface distance, Hausdorff distance, the "trimap" band) on an exact distance transform.  The
+reference ships no metric code; the definitions are those of include/him.h "Evaluation metrics" and "Distance transform
+and boundary metrics".  Every function queues device work on the current stream
 and returns device tensors; nothing synchronises with the host before ``Evaluator.summary()`` as long as every argument
 is a device tensor: a ``box`` given as a list or array (and any host tensor) is copied to the device first, which waits
 on the host.  The device calls share one cached workspace per shape and device (``ops.image_metrics`` /
@@ -149,6 +151,106 @@ def box_of_mask(mask):
     return torch.where(none[:, None], -1, box).to(torch.int32).contiguous()        # (-1, -1, -1, -1) clips to nothing
 
 
+_EDT_CHUNK_PIXELS = 1 << 26     # job pixels per him_edt call of boundary_scores: 256 MiB of int32 distances
+
+
+def _id_planes(t, keys, pred_kind=None):
+    """(B, H, W) device id planes of what ``confusion_matrix`` accepts; scores and probabilities go through
+    ``ops.label_ids`` (the arg-max and threshold rules of him_confusion)."""
+    t = _plane(_labels(t, keys))
+    if pred_kind == 'prob':
+        return ops.label_ids(t.float().reshape(-1, 1, t.shape[-2], t.shape[-1]), 'prob')
+    if t.dim() == 4 and t.shape[1] > 1:
+        return ops.label_ids(t.float(), 'scores')
+    return t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous()
+
+
+def _boundary_raw(pred, gt, classes, tol2):
+    """counts (B, n, 2, 4) int64 and sumd (B, n, 2) float64 of two (B, H, W) id planes: [..., 0, :] the boundary of the
+    prediction measured against the ground truth's, [..., 1, :] the mirror image."""
+    B, H, W = pred.shape
+    per = max(1, _EDT_CHUNK_PIXELS // (B * H * W))
+    cnt, sm = [], []
+    for i in range(0, len(classes), per):
+        part = classes[i:i + per]
+        jobs = ops.edt_jobs(B, part, 'boundary_of', pred.device)
+        d_gt = ops.distance_transform(gt, jobs)[0]
+        cp, sp = ops.boundary_stats(pred, jobs, d_gt, tol2)
+        d_pred = ops.distance_transform(pred, jobs)[0]
+        cg, sg = ops.boundary_stats(gt, jobs, d_pred, tol2)
+        cnt.append(torch.stack([cp, cg], 1).reshape(B, len(part), 2, 4))
+        sm.append(torch.stack([sp, sg], 1).reshape(B, len(part), 2))
+    return torch.cat(cnt, 1), torch.cat(sm, 1)
+
+
+def _boundary_measures(counts, sumd):
+    """precision, recall, f1, assd, hausdorff (float64) of counts (..., 2, 4) and sumd (..., 2)."""
+    c = counts.double()
+    n_p, n_g = c[..., 0, 0], c[..., 1, 0]
+    both, none = (n_p > 0) & (n_g > 0), (n_p == 0) & (n_g == 0)
+    zero, nan = torch.zeros_like(n_p), torch.full_like(n_p, float('nan'))
+    prec = torch.where(both, c[..., 0, 1] / n_p, zero)
+    rec = torch.where(both, c[..., 1, 1] / n_g, zero)
+    f1 = torch.where(prec + rec > 0, 2 * prec * rec / (prec + rec), zero)
+    assd = torch.where(both, (sumd[..., 0] + sumd[..., 1]) / (n_p + n_g), nan)
+    hd = torch.where(both, torch.sqrt(torch.maximum(c[..., 0, 2], c[..., 1, 2]).clamp(min=0)), nan)
+    return OrderedDict([('precision', torch.where(none, nan, prec)), ('recall', torch.where(none, nan, rec)),
+                        ('f1', torch.where(none, nan, f1)), ('assd', assd), ('hausdorff', hd)])
+
+
+def diag_tolerance(H, W, frac=0.0075):
+    """The usual boundary tolerance in pixels: a fraction of the image diagonal."""
+    return float(frac) * math.sqrt(float(H) * H + float(W) * W)
+
+
+def boundary_scores(pred, gt, n_class, tolerance=2.0, classes=None):
+    """Contour measures of a predicted layout per sample and class, as device tensors of shape (B, n): ``precision``,
+    ``recall``, ``f1`` (the boundary F-score within ``tolerance`` pixels), ``assd`` (average symmetric surface distance),
+    ``hausdorff``, all float64, plus the integer ``counts`` (B, n, 2, 4) and the distance sums ``sumd`` (B, n, 2) of
+    ``ops.boundary_stats`` ([..., 0, :] prediction against ground truth, [..., 1, :] the mirror image).  The boundary of
+    class c is its inner 4-neighbour boundary; definitions in include/him.h "Distance transform and boundary metrics":
+    nan where a class has no boundary in either map, zeros (and nan distances) where it has one in exactly one.
+    ``pred``, ``gt``: what ``confusion_matrix`` accepts.  ``classes``: the ids to score, default ``range(n_class)``,
+    processed in chunks that bound the distance maps to 256 MiB.  No host synchronisation (a class list that is not a run
+    of consecutive ids is copied to the device)."""
+    p = _id_planes(pred, ('comb_pred_label', 'comb_recon_label'))
+    g = _id_planes(gt, ()).to(p.device)
+    if p.shape != g.shape:
+        raise ValueError('boundary_scores: pred %s and gt %s differ' % (tuple(p.shape), tuple(g.shape)))
+    classes = list(range(int(n_class))) if classes is None else [int(c) for c in classes]
+    tol2 = int(math.floor(float(tolerance) ** 2))
+    counts, sumd = _boundary_raw(p, g, classes, tol2)
+    out = _boundary_measures(counts, sumd)
+    out['counts'], out['sumd'] = counts, sumd
+    return out
+
+
+def mask_boundary_scores(prob, gt_mask, tolerance=2.0):
+    """``boundary_scores`` of ``prob > 0.5`` against a 0 / 1 mask, shape (B,): the outline quality of a generated object
+    mask (the box2mask measure)."""
+    p = _id_planes(prob, ('obj_pred_label', 'obj_recon_label'), 'prob')
+    g = _plane(gt_mask).to(p.device)
+    g = ops.label_ids(g.float().reshape(-1, 1, g.shape[-2], g.shape[-1]), 'prob') if g.dtype == torch.float32 \
+        else g.reshape(-1, g.shape[-2], g.shape[-1]).contiguous()
+    if p.shape != g.shape:
+        raise ValueError('mask_boundary_scores: prob %s and gt_mask %s differ' % (tuple(p.shape), tuple(g.shape)))
+    counts, sumd = _boundary_raw(p, g, [1], int(math.floor(float(tolerance) ** 2)))
+    out = OrderedDict((k, v[:, 0]) for k, v in _boundary_measures(counts, sumd).items())
+    out['counts'], out['sumd'] = counts[:, 0], sumd[:, 0]
+    return out
+
+
+def boundary_band(gt, radius):
+    """fp32 (B, 1, H, W) device mask of the pixels within ``radius`` of any class boundary of ``gt`` (squared distance
+    <= floor(radius^2) to a pixel with a differing 4-neighbour), ready for ``confusion_matrix(mask=...)``: the confusion
+    matrix restricted to it gives the "trimap" IoU."""
+    g = _id_planes(gt, ())
+    dist2 = ops.distance_transform(g, rule='any_boundary')[0]
+    return (dist2 <= int(math.floor(float(radius) ** 2))).float().unsqueeze(1)
+
+
+BOUNDARY_KEYS = ('boundary_f1', 'per_class_boundary_f1', 'boundary_assd', 'mask_boundary_f1', 'mask_hausdorff')
+BAND_KEYS = ('band_mean_iou',)
 SUMMARY_KEYS = ('n_images', 'ssim', 'psnr', 'l1', 'n_layouts', 'pixel_acc', 'mean_acc', 'mean_iou', 'fw_iou',
                 'per_class_iou', 'per_class_acc', 'n_absent', 'skipped_pixels', 'n_object_masks', 'mask_iou')
 
@@ -160,9 +262,13 @@ class Evaluator(object):
     ``reconstruct`` and ``JointInference.gen_layout`` / ``gen_image`` return (a tensor, their dict, or their tuple, whose
     last entry is the generated tensor).  Nothing crosses to the host before ``summary()``."""
 
-    def __init__(self, label_nc, data_range=255., as_bytes=True):
+    def __init__(self, label_nc, data_range=255., as_bytes=True, boundary_tolerance=None, band_radius=None):
         self.label_nc, self.data_range, self.as_bytes = int(label_nc), float(data_range), bool(as_bytes)
         self._image, self._conf, self._mask, self._layouts = [], None, [], 0
+        # opt-in contour measures: the tolerance of the boundary F-score in pixels, the radius of the trimap band
+        self.boundary_tolerance = None if boundary_tolerance is None else float(boundary_tolerance)
+        self.band_radius = None if band_radius is None else float(band_radius)
+        self._bcounts, self._bsumd, self._mask_boundary, self._band = None, None, [], None
 
     def add_image(self, fake, real, box=None):
         fake = _labels(fake, ('fake_image',))
@@ -178,10 +284,27 @@ class Evaluator(object):
                               torch.zeros(2, dtype=torch.int32, device=pred_t.device))
         confusion_matrix(pred, gt, self.label_nc, mask=mask, out=self._conf)
         self._layouts += 1
+        if self.boundary_tolerance is not None:
+            bs = boundary_scores(pred, gt, self.label_nc, self.boundary_tolerance)
+            counts, sumd = bs['counts'].sum(0), bs['sumd'].sum(0)        # (n, 2, 4), (n, 2): samples pooled
+            self._bcounts = counts if self._bcounts is None else self._bcounts + counts
+            self._bsumd = sumd if self._bsumd is None else self._bsumd + sumd
+        if self.band_radius is not None:
+            band = boundary_band(gt, self.band_radius)
+            if mask is not None:
+                band = band * (mask.to(band.device).float().reshape(band.shape) != 0).float()
+            if self._band is None:
+                with torch.cuda.device(band.device):
+                    self._band = (torch.zeros((1, self.label_nc, self.label_nc), dtype=torch.int64, device=band.device),
+                                  torch.zeros(2, dtype=torch.int32, device=band.device))
+            confusion_matrix(pred, gt, self.label_nc, mask=band, out=self._band)
         return self
 
     def add_object_mask(self, prob, gt):
         self._mask.append(mask_iou(prob, gt))
+        if self.boundary_tolerance is not None:
+            bs = mask_boundary_scores(prob, gt, self.boundary_tolerance)
+            self._mask_boundary.append(torch.stack([bs['f1'], bs['hausdorff']], 1))
         return self
 
     def summary(self):
@@ -206,6 +329,16 @@ class Evaluator(object):
         if self._mask:
             m = torch.cat(self._mask, 0).cpu().numpy()
             out.update(n_object_masks=int(len(m)), mask_iou=_nanmean(m))
+        if self.boundary_tolerance is not None:
+            out.update((k, nan) for k in BOUNDARY_KEYS)
+            out['per_class_boundary_f1'] = []
+            if self._bcounts is not None:
+                out.update(_pooled_boundary(self._bcounts.cpu().numpy(), self._bsumd.cpu().numpy()))
+            if self._mask_boundary:
+                m = torch.cat(self._mask_boundary, 0).cpu().numpy()
+                out.update(mask_boundary_f1=_nanmean(m[:, 0]), mask_hausdorff=_nanmean(m[:, 1]))
+        if self.band_radius is not None:
+            out['band_mean_iou'] = segmentation_scores(self._band[0])['mean_iou'] if self._band is not None else nan
         return out
 
     def write_json(self, path):
@@ -213,6 +346,23 @@ class Evaluator(object):
             json.dump({k: (None if isinstance(v, float) and not math.isfinite(v) else v)
                        for k, v in self.summary().items()}, f, indent=1)
         return path
+
+
+def _pooled_boundary(counts, sumd):
+    """boundary_f1 (the mean over the classes with a boundary in either map), per_class_boundary_f1 (None: no boundary)
+    and boundary_assd (the mean over the classes of sum of distances / reachable boundary pixels) from counts (n, 2, 4)
+    and sums (n, 2) pooled over every sample."""
+    n_p, n_g = counts[:, 0, 0].astype(np.float64), counts[:, 1, 0].astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        prec = np.where(n_p > 0, counts[:, 0, 1] / n_p, 0.0)
+        rec = np.where(n_g > 0, counts[:, 1, 1] / n_g, 0.0)
+        f1 = np.where(prec + rec > 0, 2 * prec * rec / (prec + rec), 0.0)
+        reach = (counts[:, :, 0] - counts[:, :, 3]).sum(1).astype(np.float64)
+        assd = np.where(reach > 0, sumd.sum(1) / reach, np.nan)
+    seen = (n_p + n_g) > 0
+    return dict(boundary_f1=float(f1[seen].mean()) if seen.any() else float('nan'),
+                per_class_boundary_f1=[float(v) if k else None for v, k in zip(f1, seen)],
+                boundary_assd=_nanmean(assd))
 
 
 def _nanmean(v):
