@@ -937,6 +937,80 @@ int him_boundary_stats(const void* src, int kind, int B, int H, int W, const int
                        long long* counts, double* sumd, void* ws, size_t ws_bytes, void* stream);
 int him_label_ids(const float* src, int pred_kind, int B, int C, int H, int W, int* ids, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Set-level metrics (the reference ships none): the sliced Wasserstein distance between the Laplacian-pyramid patches of
+ * two SETS of images (Karras et al., "Progressive Growing of GANs", ICLR 2018, section 5 and its sliced_wasserstein.py).
+ * No network, no weights; everything on `stream`, no host synchronisation, no allocation, results bit-identical from
+ * run to run.  Every entry checks its arguments and returns HIM_E_INVALID / HIM_E_WORKSPACE before any launch.
+ *
+ * Pyramid of a planar fp32 batch x (B,C,H,W), C = 1 or 3.  k = [1, 4, 6, 4, 1] / 16, borders mirrored WITHOUT repeating
+ * the edge pixel (d c b | a b c d | c b a; SciPy's mode='mirror').  G_0 = x; G_{i+1} = down(G_i): filter with k in both
+ * directions and keep the even rows and columns; up(g): write g to the even positions of a zero plane of twice the size
+ * and filter with 2 k in both directions, same border rule.  L_i = G_i - up(G_{i+1}), and the last level is G_last.
+ *   him_lap_levels(H, W, want): the largest count such that the smallest level keeps min(H, W) >= 16 (0 when there is
+ *     none), or `want` when that is positive and smaller.
+ *   him_lap_level_offset(B, C, H, W, l): the element offset of level l in the packed output, the sum over i < l of
+ *     B C (H >> i) (W >> i); level l there is a dense (B, C, H >> l, W >> l) tensor.  l = levels gives the total size.
+ *   him_lap_pyramid: lap receives the `levels` Laplacian levels, packed.  gauss: NULL, or the Gaussian levels
+ *     1 .. levels - 1 packed from him_lap_level_offset(l) - him_lap_level_offset(1) (what separates down from up in a
+ *     test).  ws: him_lap_pyramid_ws bytes (the same Gaussian levels; written before it is read), 4-byte aligned.
+ *     Refused: C outside {1, 3}; levels < 1 or above him_lap_levels(H, W, 0); H or W not divisible by 2^(levels - 1);
+ *     B C H W > 2^40; a NULL x / lap / ws; a short workspace (the query returns 0 for a refused shape).
+ *     2 levels - 1 launches: down stages the 19 x 131 inputs of a tile of 8 x 64 outputs in LDS, mirror indices resolved
+ *     while staging, so a pass reads each input pixel from memory once but for the tile halo; up-and-subtract stages the
+ *     6 x 34 coarse cells of an 8 x 64 tile and evaluates the zero-insertion filter literally.
+ *
+ * Descriptors.  him_swd_gather copies, for every image b and patch p, the HIM_SWD_PATCH x HIM_SWD_PATCH x C patch of
+ * `level` (B,C,h,w) whose top-left corner is pos[b][p] = (y, x) (int32 (B,n_patches,2) on the device) into row
+ * row0 + b n_patches + p of desc (capacity, 49 C), channel-major: column c 49 + r 7 + q = level[b][c][y + r][x + q].
+ * A corner outside [0, h - 7] x [0, w - 7] is clamped into it and counted: status[0] += the number of clamped corners
+ * (an integer atomic; the caller zeroes the word).  The same pass folds the copied values into stats, 4 C doubles
+ * [sum, sum of squares, minimum, maximum] per channel, which the caller starts at [0, 0, +inf, -inf]: each image's
+ * partial is a fixed tree over the thread slots of its workgroup and a second launch adds the partials to stats in
+ * image order, so a set streamed in any batch sizes ends with the same bits.  ws: him_swd_gather_ws(B, C) bytes, 8-byte
+ * aligned.  Refused: C outside {1, 3}, h or w < 7, n_patches outside 1..65536, rows outside [0, capacity).
+ *
+ * Normalisation and projection.  him_swd_project derives per channel, in double, mean = sum / (49 N) and the POPULATION
+ * deviation sqrt(sum2 / (49 N) - mean^2) from stats and writes
+ *   out[d][n] = sum_k dirs[k][d] * (desc[n][k] - mean[c(k)]) / deviation[c(k)],  c(k) = k / 49,
+ * for the first N rows of desc: dirs is fp32 (49 C, n_dirs), out fp32 (n_dirs, N), direction-major so that every
+ * direction is one contiguous segment for the sort.  A channel with minimum == maximum (or a deviation that is not
+ * positive) sets HIM_SWD_ZERO_DEVIATION in status[0] (atomic or; the caller zeroes the word) and makes every output
+ * NaN.  Plain FMA in double, k ascending: K = 49 C <= 147 is too short for a matrix-core pipeline to repay its operand
+ * shuffles, and double keeps the result within one rounding of the exact sum.  N * n_dirs <= 2^31 - 1.
+ *
+ * him_sort_segments sorts S contiguous segments of N fp32 keys each, in place, ascending in the order of the sign-fixed
+ * bit pattern  key(b) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000)  compared as unsigned: NaNs with the sign bit, -inf,
+ * negative values, -0, +0, positive values, +inf, NaNs without the sign bit.  Bits are moved, never changed.  status[0] =
+ * the number of NaNs among the keys (written by the call).  Not stable (there is no payload to tell).  Two regimes:
+ * N <= HIM_SORT_LDS_MAX: one workgroup per segment, a bitonic network in LDS; longer segments: chunks of HIM_SORT_LDS_MAX
+ * keys sorted the same way, then ceil(log2(chunks)) merge passes through global memory between keys and ws, every key
+ * finding its slot by a binary search of the partner run.  ws: him_sort_segments_ws(S, N) bytes (16 in the LDS regime,
+ * S N floats beyond), 4-byte aligned.  Refused: S or N < 1, S * N > 2^31 - 1, a short workspace.
+ *
+ * him_swd_distance: a, b fp32 (n_dirs, N), each direction sorted.  dir_sums[d] = sum_n |a[d][n] - b[d][n]| in double
+ * (thread t of the direction's workgroup adds n = t, t + 256, ..., then a fixed tree); mean[0] = sum_d dir_sums[d] /
+ * (n_dirs N), the level's distance.  Na != Nb is refused.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_SWD_PATCH 7
+#define HIM_LAP_MAX_LEVELS 12
+#define HIM_SORT_LDS_MAX 8192
+#define HIM_SWD_ZERO_DEVIATION 1
+unsigned him_lap_levels(int H, int W, int want);
+long long him_lap_level_offset(int B, int C, int H, int W, int level);
+size_t him_lap_pyramid_ws(int B, int C, int H, int W, int levels);
+int him_lap_pyramid(const float* x, int B, int C, int H, int W, int levels, float* lap, float* gauss, void* ws,
+                    size_t ws_bytes, void* stream);
+size_t him_swd_gather_ws(int B, int C);
+int him_swd_gather(const float* level, int B, int C, int h, int w, const int* pos, int n_patches, float* desc,
+                   long long capacity, long long row0, double* stats, int* status, void* ws, size_t ws_bytes, void* stream);
+int him_swd_project(const float* desc, long long N, int C, const double* stats, const float* dirs, int n_dirs, float* out,
+                    int* status, void* stream);
+size_t him_sort_segments_ws(long long S, long long N);
+int him_sort_segments(float* keys, long long S, long long N, int* status, void* ws, size_t ws_bytes, void* stream);
+int him_swd_distance(const float* a, long long Na, const float* b, long long Nb, int n_dirs, double* dir_sums, double* mean,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,16 @@ _SIGS = {
     'him_boundary_stats_workspace': (c_size_t, [c_int, c_int, c_int]),
     'him_boundary_stats': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, c_size_t, P]),
     'him_label_ids': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'him_lap_levels': (C.c_uint, [c_int, c_int, c_int]),
+    'him_lap_level_offset': (C.c_longlong, [c_int] * 5),
+    'him_lap_pyramid_ws': (c_size_t, [c_int] * 5),
+    'him_lap_pyramid': (c_int, [P] + [c_int] * 5 + [P, P, P, c_size_t, P]),
+    'him_swd_gather_ws': (c_size_t, [c_int, c_int]),
+    'him_swd_gather': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, C.c_longlong, C.c_longlong, P, P, P, c_size_t, P]),
+    'him_swd_project': (c_int, [P, C.c_longlong, c_int, P, P, c_int, P, P, P]),
+    'him_sort_segments_ws': (c_size_t, [C.c_longlong, C.c_longlong]),
+    'him_sort_segments': (c_int, [P, C.c_longlong, C.c_longlong, P, P, c_size_t, P]),
+    'him_swd_distance': (c_int, [P, C.c_longlong, P, C.c_longlong, c_int, P, P, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

@@ -2898,3 +2898,140 @@ def label_ids(pred, pred_kind):
         ids = torch.empty((B, H, W), dtype=torch.int32, device=pred.device)
         lib.him_label_ids(_p(pred), 4 if pred_kind == 'scores' else 5, B, C, H, W, _p(ids), _stream())
     return ids
+
+
+# -- set-level metrics: Laplacian pyramid, segmented sort, sliced Wasserstein distance (include/him.h "Set-level metrics")
+SWD_PATCH, SORT_LDS_MAX, SWD_ZERO_DEVIATION = 7, 8192, 1
+_SWD_WS = {}            # (tag, shape..., device index) -> cached workspace; one stream at a time per shape
+
+
+def _swd_ws(key, nbytes, device):
+    key = key + (torch.cuda.current_device(),)
+    ws = _SWD_WS.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _SWD_WS[key] = torch.empty(max((int(nbytes) + 7) // 8, 2), dtype=torch.float64, device=device)
+    return ws
+
+
+def _swd_f32(t, what, dim):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('%s must be a device tensor' % what)
+    if t.dtype != torch.float32 or t.dim() != dim:
+        raise ValueError('%s must be a %d-dimensional fp32 tensor, got %s %s' % (what, dim, t.dtype, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def lap_levels(H, W, levels=None):
+    """The number of pyramid levels of an H x W image: the most that keep min(H, W) >= 16, or ``levels`` if smaller."""
+    return int(lib.him_lap_levels(int(H), int(W), 0 if levels is None else int(levels)))
+
+
+def lap_pyramid(x, levels=None, want_gauss=False):
+    """The Laplacian pyramid of a planar fp32 device batch (B, C, H, W), C = 1 or 3: a list of ``levels`` tensors
+    (B, C, H >> l, W >> l), finest first, views of one packed buffer; with ``want_gauss`` also the list of the Gaussian
+    levels 1 .. levels - 1.  Five-tap binomial filter, mirrored borders; the last level is the Gaussian one.  H and W
+    must be divisible by 2^(levels - 1).  Current stream, no host synchronisation, no autograd."""
+    x = _swd_f32(x, 'lap_pyramid: x', 4)
+    B, C, H, W = x.shape
+    L = lap_levels(H, W, levels)
+    if levels is not None and int(levels) != L:
+        raise ValueError('lap_pyramid: %d levels asked, an image of %d x %d has %d' % (int(levels), H, W, L))
+    need = int(lib.him_lap_pyramid_ws(B, C, H, W, L)) if L >= 1 else 0
+    if need == 0:
+        raise ValueError('lap_pyramid: (B, C, H, W) = %s refused: C is 1 or 3, min(H, W) >= 16, and H and W are '
+                         'divisible by 2^(levels - 1)' % (tuple(x.shape),))
+    off = [int(lib.him_lap_level_offset(B, C, H, W, l)) for l in range(L + 1)]
+    with torch.cuda.device(x.device):
+        ws = _swd_ws(('lap', B, C, H, W, L), need, x.device)
+        lap = torch.empty(off[L], dtype=torch.float32, device=x.device)
+        gauss = torch.empty(max(off[L] - off[1], 1), dtype=torch.float32, device=x.device) if want_gauss else None
+        lib.him_lap_pyramid(_p(x), B, C, H, W, L, _p(lap), _p(gauss), _p(ws), ws.numel() * 8, _stream())
+    laps = [lap[off[l]:off[l + 1]].view(B, C, H >> l, W >> l) for l in range(L)]
+    if not want_gauss:
+        return laps
+    return laps, [gauss[off[l] - off[1]:off[l + 1] - off[1]].view(B, C, H >> l, W >> l) for l in range(1, L)]
+
+
+def swd_stats(C, device):
+    """Fresh channel accumulators of ``swd_gather``: (C, 4) float64 [sum, sum of squares, minimum, maximum]."""
+    with torch.cuda.device(device):
+        return torch.tensor([[0.0, 0.0, float('inf'), float('-inf')]] * int(C), dtype=torch.float64).to(device)
+
+
+def swd_gather(level, pos, desc, row0, stats, status):
+    """Copies the 7 x 7 x C patches of ``level`` (B, C, h, w) at the corners ``pos`` (B, n, 2) int32 (y, x) into the rows
+    ``row0 ...`` of ``desc`` (capacity, 49 C), folds them into ``stats`` (``swd_stats``) and adds the number of clamped
+    corners to the int32 ``status[0]``.  Everything on the device and in place; returns the row behind the last one."""
+    level = _swd_f32(level, 'swd_gather: level', 4)
+    B, C, h, w = level.shape
+    if not torch.is_tensor(pos) or pos.dtype != torch.int32 or pos.dim() != 3 or pos.shape[0] != B or pos.shape[2] != 2 \
+            or pos.device != level.device:
+        raise ValueError('swd_gather: pos must be a (B, n_patches, 2) int32 tensor on the device of level')
+    n = pos.shape[1]
+    if desc.dtype != torch.float32 or desc.dim() != 2 or desc.shape[1] != 49 * C or not desc.is_contiguous() \
+            or desc.device != level.device:
+        raise ValueError('swd_gather: desc must be a contiguous (capacity, %d) fp32 tensor on the device of level' % (49 * C))
+    if stats.dtype != torch.float64 or tuple(stats.shape) != (C, 4) or not stats.is_contiguous() \
+            or status.dtype != torch.int32 or not status.is_cuda:
+        raise ValueError('swd_gather: stats must be (C, 4) float64 and status int32, both on the device')
+    pos = pos.contiguous()
+    with torch.cuda.device(level.device):
+        need = int(lib.him_swd_gather_ws(B, C))
+        ws = _swd_ws(('gather', B, C), need, level.device)
+        lib.him_swd_gather(_p(level), B, C, h, w, _p(pos), n, _p(desc), desc.shape[0], int(row0), _p(stats), _p(status),
+                           _p(ws), ws.numel() * 8, _stream())
+    return int(row0) + B * n
+
+
+def swd_project(desc, stats, dirs, status=None):
+    """``(out, status)``: the (n_dirs, N) fp32 projections of the N rows of ``desc`` (N, 49 C), normalised per channel
+    with the mean and population deviation derived on the device from ``stats``, onto the columns of ``dirs``
+    (49 C, n_dirs).  ``status[0]`` gains SWD_ZERO_DEVIATION (and ``out`` is NaN) when a channel does not vary."""
+    desc, dirs = _swd_f32(desc, 'swd_project: desc', 2), _swd_f32(dirs, 'swd_project: dirs', 2)
+    N, K = desc.shape
+    if K not in (49, 147) or dirs.shape[0] != K or N < 1:
+        raise ValueError('swd_project: desc %s against dirs %s' % (tuple(desc.shape), tuple(dirs.shape)))
+    with torch.cuda.device(desc.device):
+        out = torch.empty((dirs.shape[1], N), dtype=torch.float32, device=desc.device)
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=desc.device)
+        lib.him_swd_project(_p(desc), N, K // 49, _p(stats), _p(dirs), dirs.shape[1], _p(out), _p(status), _stream())
+    return out, status
+
+
+def sort_segments(keys):
+    """Sorts every row of the (S, N) (or (N,)) fp32 device tensor ``keys`` in place, ascending in the order of the
+    sign-fixed bit pattern (-0 before +0, +inf before NaN); returns ``(keys, status)`` with the int32 ``status[0]`` the
+    number of NaNs.  Rows of up to SORT_LDS_MAX keys are sorted in LDS, longer ones by merge passes through a cached
+    workspace of the size of ``keys``.  Exact, identical bits from run to run.  Current stream, no host synchronisation."""
+    if not torch.is_tensor(keys) or not keys.is_cuda:
+        raise ValueError('sort_segments: keys must be a device tensor')
+    if keys.dtype != torch.float32 or keys.dim() not in (1, 2) or not keys.is_contiguous() or keys.numel() == 0:
+        raise ValueError('sort_segments: keys must be a contiguous, non-empty (S, N) or (N,) fp32 tensor')
+    S, N = (1, keys.shape[0]) if keys.dim() == 1 else keys.shape
+    if S * N > 2 ** 31 - 1:
+        raise ValueError('sort_segments: %d x %d keys, at most 2^31 - 1 per call' % (S, N))
+    with torch.cuda.device(keys.device):
+        need = int(lib.him_sort_segments_ws(S, N))
+        ws = _swd_ws(('sort',), need, keys.device)
+        status = torch.empty(1, dtype=torch.int32, device=keys.device)
+        lib.him_sort_segments(_p(keys), S, N, _p(status), _p(ws), ws.numel() * 8, _stream())
+    return keys, status
+
+
+def sliced_wasserstein(desc_a, desc_b, stats_a, stats_b, dirs):
+    """One level's sliced Wasserstein distance between two descriptor sets: ``(distance, dir_sums, status)`` on the
+    device, a float64 scalar (NaN when a channel of either set does not vary), the (n_dirs,) float64 sums of
+    |a_sorted - b_sorted| and the int32 flag word of ``swd_project``.  Both sets must hold the same number of rows."""
+    if desc_a.shape[0] != desc_b.shape[0]:
+        raise ValueError('sliced_wasserstein: the sets hold %d and %d descriptors' % (desc_a.shape[0], desc_b.shape[0]))
+    pa, status = swd_project(desc_a, stats_a, dirs)
+    pb, _ = swd_project(desc_b, stats_b, dirs, status)
+    sort_segments(pa)
+    sort_segments(pb)
+    n_dirs, N = pa.shape
+    with torch.cuda.device(pa.device):
+        dir_sums = torch.empty(n_dirs, dtype=torch.float64, device=pa.device)
+        mean = torch.empty((), dtype=torch.float64, device=pa.device)
+        lib.him_swd_distance(_p(pa), N, _p(pb), N, n_dirs, _p(dir_sums), _p(mean), _stream())
+    return mean, dir_sums, status

@@ -249,6 +249,90 @@ def boundary_band(gt, radius):
     return (dist2 <= int(math.floor(float(radius) ** 2))).float().unsqueeze(1)
 
 
+def swd_tables(seed, C, n_dirs=512, device='cuda'):
+    """The direction table of the sliced Wasserstein distance: (49 C, n_dirs) fp32 on ``device``, every column a seeded
+    normal draw (``numpy.random.RandomState(seed)``, float64) scaled to unit length.  Drawn on the host, uploaded once."""
+    d = np.random.RandomState(int(seed) & 0x7fffffff).randn(int(n_dirs), 49 * int(C))
+    d /= np.sqrt((d * d).sum(1, keepdims=True))
+    return torch.from_numpy(np.ascontiguousarray(d.T).astype(np.float32)).to(device)
+
+
+def swd_positions(seed, index, B, n_patches, h, w, level=0, which=0, device=None):
+    """The patch corners (B, n_patches, 2) int32 (y, x) of the images ``index .. index + B - 1`` of set ``which`` on a
+    level of h x w: uniform over [0, h - 7] x [0, w - 7], one seeded host generator per (seed, set, level, image), so
+    the table of an image does not depend on how the set is cut into batches.  A host array, or a device tensor."""
+    out = np.empty((int(B), int(n_patches), 2), np.int32)
+    for b in range(int(B)):
+        rs = np.random.RandomState([int(seed) & 0x7fffffff, int(which), int(level), int(index) + b])
+        out[b, :, 0] = rs.randint(0, h - 6, int(n_patches))
+        out[b, :, 1] = rs.randint(0, w - 6, int(n_patches))
+    return out if device is None else torch.from_numpy(out).to(device)
+
+
+class SlicedWasserstein(object):
+    """Streams two image sets (``add(fake, real)``, batch by batch) into per-level descriptor matrices on the device and
+    gives the sliced Wasserstein distance of every Laplacian level (include/him.h "Set-level metrics").  The buffers
+    grow geometrically on the device; nothing goes to the host."""
+
+    def __init__(self, n_patches=128, n_dirs=512, levels=None, seed=0, same_positions=False):
+        self.n_patches, self.n_dirs, self.seed = int(n_patches), int(n_dirs), int(seed)
+        self.want_levels, self.same_positions = levels, bool(same_positions)
+        self.n_images, self.shape, self.levels, self.dirs = 0, None, 0, None
+        self._desc, self._stats, self._rows, self.clamped = None, None, 0, None
+
+    def add(self, fake, real):
+        fake, real = _image_pair(fake, real)
+        if fake.shape != real.shape:
+            raise ValueError('sliced_wasserstein: fake %s and real %s differ' % (tuple(fake.shape), tuple(real.shape)))
+        B, C, H, W = fake.shape
+        dev, n = fake.device, self.n_patches
+        if self.shape is None:
+            self.shape, self.levels = (C, H, W), ops.lap_levels(H, W, self.want_levels)
+            self.dirs = swd_tables(self.seed, C, self.n_dirs, dev)
+            self._desc = [[None, None] for _ in range(self.levels)]
+            self._stats = [[ops.swd_stats(C, dev), ops.swd_stats(C, dev)] for _ in range(self.levels)]
+            with torch.cuda.device(dev):
+                self.clamped = torch.zeros(1, dtype=torch.int32, device=dev)
+        elif self.shape != (C, H, W):
+            raise ValueError('sliced_wasserstein: images of %s after images of %s' % ((C, H, W), self.shape))
+        need = self._rows + B * n
+        for which, x in enumerate((fake, real)):
+            for l, lv in enumerate(ops.lap_pyramid(x, self.levels)):
+                pos = swd_positions(self.seed, self.n_images, B, n, H >> l, W >> l, l,
+                                    0 if self.same_positions else which, dev)
+                desc = self._desc[l][which]
+                if desc is None or desc.shape[0] < need:
+                    with torch.cuda.device(dev):
+                        grown = torch.empty((max(need, 2 * (0 if desc is None else desc.shape[0])), 49 * C),
+                                            dtype=torch.float32, device=dev)
+                    if desc is not None:
+                        grown[:self._rows].copy_(desc[:self._rows])
+                    desc = self._desc[l][which] = grown
+                ops.swd_gather(lv, pos, desc, self._rows, self._stats[l][which], self.clamped)
+        self._rows, self.n_images = need, self.n_images + B
+        return self
+
+    @property
+    def n_descriptors(self):
+        return self._rows
+
+    def distances(self):
+        """(levels,) float64 on the device, finest level first; NaN for a level with a channel that does not vary."""
+        if not self._rows:
+            raise ValueError('sliced_wasserstein: no images were added')
+        return torch.stack([ops.sliced_wasserstein(d[0][:self._rows], d[1][:self._rows], s[0], s[1], self.dirs)[0]
+                            for d, s in zip(self._desc, self._stats)])
+
+
+def sliced_wasserstein(fake, real, n_patches=128, n_dirs=512, levels=None, seed=0, same_positions=False):
+    """The sliced Wasserstein distance between two whole image sets (N, C, H, W), C = 1 or 3, per Laplacian level:
+    (levels,) float64 on the device, finest first (Karras et al. 2018 report these times 1e3).  ``n_patches`` 7 x 7
+    patches per image and level, normalised per set, level and channel, projected onto ``n_dirs`` seeded unit directions,
+    sorted, and compared rank by rank.  ``same_positions`` uses one corner table for both sets."""
+    return SlicedWasserstein(n_patches, n_dirs, levels, seed, same_positions).add(fake, real).distances()
+
+
+SWD_KEYS = ('swd', 'swd_levels', 'swd_descriptors')
 BOUNDARY_KEYS = ('boundary_f1', 'per_class_boundary_f1', 'boundary_assd', 'mask_boundary_f1', 'mask_hausdorff')
 BAND_KEYS = ('band_mean_iou',)
 SUMMARY_KEYS = ('n_images', 'ssim', 'psnr', 'l1', 'n_layouts', 'pixel_acc', 'mean_acc', 'mean_iou', 'fw_iou',
@@ -262,18 +346,22 @@ class Evaluator(object):
     ``reconstruct`` and ``JointInference.gen_layout`` / ``gen_image`` return (a tensor, their dict, or their tuple, whose
     last entry is the generated tensor).  Nothing crosses to the host before ``summary()``."""
 
-    def __init__(self, label_nc, data_range=255., as_bytes=True, boundary_tolerance=None, band_radius=None):
+    def __init__(self, label_nc, data_range=255., as_bytes=True, boundary_tolerance=None, band_radius=None, swd=None):
         self.label_nc, self.data_range, self.as_bytes = int(label_nc), float(data_range), bool(as_bytes)
         self._image, self._conf, self._mask, self._layouts = [], None, [], 0
         # opt-in contour measures: the tolerance of the boundary F-score in pixels, the radius of the trimap band
         self.boundary_tolerance = None if boundary_tolerance is None else float(boundary_tolerance)
         self.band_radius = None if band_radius is None else float(band_radius)
         self._bcounts, self._bsumd, self._mask_boundary, self._band = None, None, [], None
+        # opt-in set-level measure: True, or a dict of n_patches, n_dirs, levels, seed, same_positions
+        self._swd = None if swd is None or swd is False else SlicedWasserstein(**({} if swd is True else dict(swd)))
 
     def add_image(self, fake, real, box=None):
         fake = _labels(fake, ('fake_image',))
         sums, _ = image_sums(fake, real, self.data_range, self.as_bytes, box)
         self._image.append(sums.sum(1))                               # (B, 5): channels pooled
+        if self._swd is not None:
+            self._swd.add(fake, real)                                 # whole images, as the tensors stand
         return self
 
     def add_layout(self, pred, gt, mask=None):
@@ -339,6 +427,11 @@ class Evaluator(object):
                 out.update(mask_boundary_f1=_nanmean(m[:, 0]), mask_hausdorff=_nanmean(m[:, 1]))
         if self.band_radius is not None:
             out['band_mean_iou'] = segmentation_scores(self._band[0])['mean_iou'] if self._band is not None else nan
+        if self._swd is not None:
+            out.update(swd=nan, swd_levels=[], swd_descriptors=int(self._swd.n_descriptors))
+            if self._swd.n_descriptors:
+                lv = self._swd.distances().cpu().numpy() * 1e3           # as the paper reports them
+                out.update(swd=float(lv.mean()), swd_levels=[float(v) for v in lv])
         return out
 
     def write_json(self, path):
@@ -373,7 +466,8 @@ def _nanmean(v):
 
 def evaluate_mask2image(model, dataset, how_many, evaluator=None):
     """The loop of the reference's vis_mask2image.py (``model.inference`` per sample of ``dataset``, batch 1, the first
-    ``how_many`` samples) feeding an ``Evaluator``: generated against real image inside the edited box.  The box is the
+    ``how_many`` samples) feeding an ``Evaluator`` (passed through as it is: one built with ``swd=...`` also collects the
+    set-level sliced Wasserstein distance): generated against real image inside the edited box.  The box is the
     loader's ``input_bbox`` when the sample carries one, else the extent of ``mask_in``.  Returns the evaluator."""
     ev = evaluator if evaluator is not None else Evaluator(getattr(model.opt, 'label_nc', 35))
     for i, data in enumerate(dataset):
