@@ -1011,6 +1011,55 @@ int him_sort_segments(float* keys, long long S, long long N, int* status, void* 
 int him_swd_distance(const float* a, long long Na, const float* b, long long Nb, int n_dirs, double* dir_sums, double* mean,
                      void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Feature-space set metrics (the reference ships none): the distance between a generated and a real SET in the feature
+ * space of a frozen network -- KID (Binkowski et al., "Demystifying MMD GANs", ICLR 2018: the unbiased MMD^2 estimate
+ * with the kernel k(x, y) = (gamma x.y + coef0)^3) and the Frechet distance between the Gaussians fitted to the two sets
+ * (Heusel et al. 2017; FID's formula on whatever features are supplied).  Everything on `stream`, no host
+ * synchronisation, no allocation, no floating-point atomics, results bit-identical from run to run.  Every entry checks
+ * its arguments and returns HIM_E_INVALID / HIM_E_WORKSPACE, with a him_last_error() text that names it, before any
+ * launch: a refused call writes nothing.
+ *
+ * him_feat_pool: feat[(row0 + b) D + c0 + c] = the mean over the h w plane of x[b][c], x planar fp32 (B,C,h,w), summed
+ * in double (thread t of the plane's workgroup adds elements t, t + 256, ..., then a fixed tree) and rounded to fp32
+ * once.  feat is a (capacity, D) fp32 matrix; several feature maps are concatenated into one row by one call each with
+ * its own c0.  Nothing else of feat is written.  Refused: a size < 1, h w > 2^31 - 1, B C h w > 2^40,
+ * row0 < 0 or row0 + B > capacity, c0 < 0 or c0 + C > D.
+ *
+ * him_feat_moments ADDS to the float64 accumulators sum[D] and second[D D] the column sums and X^T X of the rows
+ * row0 .. row0 + n - 1 of the fp32 matrix feat with row length D, so that a set can be streamed batch by batch (the
+ * caller starts both at zero).  second is the full matrix; its two triangles receive the same bits (a wave computes a
+ * 16 x 16 tile of the upper triangle and writes it and its mirror image).  The products run on v_mfma_f64_16x16x4_f64
+ * with the operands widened fp32 -> fp64 on load: every product is exact, only the summation (rows ascending, four per
+ * instruction) rounds.  1 <= D <= HIM_FEAT_MAX_DIM; neither D nor n need be a multiple of the tile: the padding lives
+ * in registers and nothing is read past a row or past the last row.  ws: him_feat_moments_ws(n, D) bytes, 8-byte
+ * aligned (16 bytes today: one wave owns a tile for all n rows, so there are no partials to park; 0 for a refused
+ * shape).
+ *
+ * him_kid_sums: x (nx, D) and y (ny, D) fp32; ix, iy int32 (n_subsets, m) row indices into x and y.  For subset s
+ *   out[3 s + 0] = sum_{i != j} k(x_ix[s][i], x_ix[s][j]),   out[3 s + 1] = the same over y and iy,
+ *   out[3 s + 2] = sum_{i, j} k(x_ix[s][i], y_iy[s][j]),     k(a, b) = (gamma a.b + coef0)^3,
+ * float64, i and j POSITIONS in the subset (the diagonal is excluded by position, not by row index), every sum over
+ * ordered pairs.  gamma == 0 means 1 / D.  The dot products run on v_mfma_f64_16x16x4_f64 (exact products, k
+ * ascending in groups of sixteen columns), the cube and both masks on the accumulators; a workgroup owns a 64 x 64 tile
+ * of pairs and leaves one partial in ws (tiles below the diagonal of the two symmetric blocks are skipped, those above
+ * count twice, which is exact), and a second launch adds a subset's partials in tile order.  An index outside [0, nx)
+ * (or [0, ny)) is never dereferenced: it sets HIM_KID_BAD_INDEX in the int32 status[0] (atomic or; the caller zeroes
+ * the word) and makes the three sums of its subset NaN; other subsets are unaffected.  ws: him_kid_sums_ws(n_subsets, m)
+ * bytes, 8-byte aligned.  Refused: m outside 2..65536, n_subsets outside 1..65535, D outside 1..2^20, nx or ny outside
+ * 1..2^31 - 1, a negative or non-finite gamma, a non-finite coef0, a short workspace.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_FEAT_MAX_DIM 4096
+#define HIM_KID_BAD_INDEX 1
+int him_feat_pool(const float* x, int B, int C, int h, int w, float* feat, long long capacity, long long row0, int D, int c0,
+                  void* stream);
+size_t him_feat_moments_ws(long long n, int D);
+int him_feat_moments(const float* feat, long long row0, long long n, int D, double* sum, double* second, void* ws,
+                     size_t ws_bytes, void* stream);
+size_t him_kid_sums_ws(int n_subsets, int m);
+int him_kid_sums(const float* x, long long nx, const float* y, long long ny, int D, const int* ix, const int* iy, int n_subsets,
+                 int m, double gamma, double coef0, double* out, int* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

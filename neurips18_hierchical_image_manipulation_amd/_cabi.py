@@ -166,6 +166,12 @@ _SIGS = {
     'him_sort_segments_ws': (c_size_t, [C.c_longlong, C.c_longlong]),
     'him_sort_segments': (c_int, [P, C.c_longlong, C.c_longlong, P, P, c_size_t, P]),
     'him_swd_distance': (c_int, [P, C.c_longlong, P, C.c_longlong, c_int, P, P, P]),
+    'him_feat_pool': (c_int, [P, c_int, c_int, c_int, c_int, P, C.c_longlong, C.c_longlong, c_int, c_int, P]),
+    'him_feat_moments_ws': (c_size_t, [C.c_longlong, c_int]),
+    'him_feat_moments': (c_int, [P, C.c_longlong, C.c_longlong, c_int, P, P, P, c_size_t, P]),
+    'him_kid_sums_ws': (c_size_t, [c_int, c_int]),
+    'him_kid_sums': (c_int, [P, C.c_longlong, P, C.c_longlong, c_int, P, P, c_int, c_int, C.c_double, C.c_double, P, P, P,
+                             c_size_t, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

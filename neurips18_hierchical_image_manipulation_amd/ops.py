@@ -3035,3 +3035,99 @@ def sliced_wasserstein(desc_a, desc_b, stats_a, stats_b, dirs):
         mean = torch.empty((), dtype=torch.float64, device=pa.device)
         lib.him_swd_distance(_p(pa), N, _p(pb), N, n_dirs, _p(dir_sums), _p(mean), _stream())
     return mean, dir_sums, status
+
+
+# -- feature-space set metrics: descriptor pooling, streaming moments, KID kernel sums (include/him.h "Feature-space set
+# metrics")
+FEAT_MAX_DIM, KID_BAD_INDEX = 4096, 1
+
+
+def _feat_matrix(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('%s must be a device tensor' % what)
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[1] < 1:
+        raise ValueError('%s must be a contiguous (rows, D) fp32 tensor, got %s %s' % (what, t.dtype, tuple(t.shape)))
+    return t.detach()
+
+
+def feat_pool(x, feat, row0, c0=0):
+    """Writes the plane means of the fp32 device feature maps ``x`` (B, C, h, w) to ``feat[row0 + b, c0 + c]`` of the
+    contiguous (capacity, D) fp32 device matrix ``feat``, in place: summed in double, rounded once.  Several maps are
+    concatenated into one row by one call each with its own ``c0``.  Returns the column behind the last one written.
+    Current stream, no host synchronisation, no autograd."""
+    x = _swd_f32(x, 'feat_pool: x', 4)
+    feat = _feat_matrix(feat, 'feat_pool: feat')
+    if feat.device != x.device:
+        raise ValueError('feat_pool: feat must be on the device of x')
+    B, C, h, w = x.shape
+    row0, c0 = int(row0), int(c0)
+    if B < 1 or C < 1 or h < 1 or w < 1 or row0 < 0 or row0 + B > feat.shape[0] or c0 < 0 or c0 + C > feat.shape[1]:
+        raise ValueError('feat_pool: x %s does not fit rows [%d, %d) and columns [%d, %d) of feat %s'
+                         % (tuple(x.shape), row0, row0 + B, c0, c0 + C, tuple(feat.shape)))
+    with torch.cuda.device(x.device):
+        lib.him_feat_pool(_p(x), B, C, h, w, _p(feat), feat.shape[0], row0, feat.shape[1], c0, _stream())
+    return c0 + C
+
+
+def feat_moment_buffers(D, device):
+    """Fresh accumulators of ``feat_moments``: ``(sum (D,), second (D, D))`` float64 zeros on ``device``."""
+    D = int(D)
+    if D < 1 or D > FEAT_MAX_DIM:
+        raise ValueError('feat_moments: D %d outside 1..%d' % (D, FEAT_MAX_DIM))
+    with torch.cuda.device(device):
+        return torch.zeros(D, dtype=torch.float64, device=device), torch.zeros((D, D), dtype=torch.float64, device=device)
+
+
+def feat_moments(feat, row0, n, sum, second):
+    """Adds the column sums and X^T X of the rows ``row0 .. row0 + n - 1`` of the (rows, D) fp32 device matrix ``feat``
+    to the float64 device accumulators ``sum`` (D,) and ``second`` (D, D) (``feat_moment_buffers``), in place; exact
+    products on the fp64 matrix instruction, both triangles of ``second`` identical.  Returns ``(sum, second)``."""
+    feat = _feat_matrix(feat, 'feat_moments: feat')
+    D, row0, n = feat.shape[1], int(row0), int(n)
+    if D > FEAT_MAX_DIM:
+        raise ValueError('feat_moments: D %d outside 1..%d' % (D, FEAT_MAX_DIM))
+    if n < 1 or row0 < 0 or row0 + n > feat.shape[0]:
+        raise ValueError('feat_moments: rows [%d, %d) outside feat %s' % (row0, row0 + n, tuple(feat.shape)))
+    for t, shape, what in ((sum, (D,), 'sum'), (second, (D, D), 'second')):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() \
+                or t.device != feat.device:
+            raise ValueError('feat_moments: %s must be a contiguous %s float64 tensor on the device of feat' % (what, shape))
+    with torch.cuda.device(feat.device):
+        need = int(lib.him_feat_moments_ws(n, D))
+        ws = _swd_ws(('moments',), need, feat.device)
+        lib.him_feat_moments(_p(feat), row0, n, D, _p(sum), _p(second), _p(ws), ws.numel() * 8, _stream())
+    return sum, second
+
+
+def kid_sums(x, y, ix, iy, gamma=0.0, coef0=1.0, status=None):
+    """``(out, status)``: for every row s of the int32 device index tables ``ix`` / ``iy`` (n_subsets, m) the float64
+    sums ``out[s] = [sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)]`` over the indexed rows
+    of the fp32 device matrices ``x`` (nx, D) and ``y`` (ny, D), k(a, b) = (gamma a.b + coef0)^3, ``gamma == 0`` meaning
+    1 / D; the diagonal is excluded by position.  Dot products on the fp64 matrix instruction; the Gram matrix is never
+    stored.  An index outside its matrix sets KID_BAD_INDEX in the int32 ``status[0]`` and makes its subset NaN."""
+    x, y = _feat_matrix(x, 'kid_sums: x'), _feat_matrix(y, 'kid_sums: y')
+    if y.device != x.device or y.shape[1] != x.shape[1] or x.shape[0] < 1 or y.shape[0] < 1:
+        raise ValueError('kid_sums: x %s and y %s must be non-empty, of one row length and on one device'
+                         % (tuple(x.shape), tuple(y.shape)))
+    for t in (ix, iy):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError('kid_sums: ix and iy must be device tensors')
+        if t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous() or t.device != x.device or t.shape != ix.shape:
+            raise ValueError('kid_sums: ix and iy must be contiguous (n_subsets, m) int32 tensors of one shape on the '
+                             'device of x')
+    n_subsets, m = ix.shape
+    gamma, coef0 = float(gamma), float(coef0)
+    with torch.cuda.device(x.device):
+        need = int(lib.him_kid_sums_ws(n_subsets, m))
+        if need == 0 or not 0.0 <= gamma < float('inf') or coef0 != coef0 or abs(coef0) == float('inf'):
+            raise ValueError('kid_sums: n_subsets %d (1..65535), m %d (2..65536), gamma %r (>= 0), coef0 %r (finite)'
+                             % (n_subsets, m, gamma, coef0))
+        ws = _swd_ws(('kid', n_subsets, m), need, x.device)
+        out = torch.empty((n_subsets, 3), dtype=torch.float64, device=x.device)
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=x.device)
+        elif not torch.is_tensor(status) or status.dtype != torch.int32 or not status.is_cuda:
+            raise ValueError('kid_sums: status must be an int32 device tensor')
+        lib.him_kid_sums(_p(x), x.shape[0], _p(y), y.shape[0], x.shape[1], _p(ix), _p(iy), n_subsets, m, gamma, coef0,
+                         _p(out), _p(status), _p(ws), ws.numel() * 8, _stream())
+    return out, status

@@ -332,6 +332,178 @@ def sliced_wasserstein(fake, real, n_patches=128, n_dirs=512, levels=None, seed=
     return SlicedWasserstein(n_patches, n_dirs, levels, seed, same_positions).add(fake, real).distances()
 
 
+def kid_subsets(seed, which, n, n_subsets, subset_size):
+    """The subset table of KID: (n_subsets, subset_size) int32 on the host, row s a draw without replacement from
+    ``range(n)`` by ``numpy.random.RandomState([seed, which, s])`` (``which``: 0 the generated set, 1 the real one).
+    Seeded on the host and uploaded once, like ``swd_positions``; it depends on the size of the set only, not on how
+    the set was batched."""
+    n, n_subsets, subset_size = int(n), int(n_subsets), int(subset_size)
+    if not 1 <= subset_size <= n or n_subsets < 1:
+        raise ValueError('kid_subsets: %d subsets of %d rows out of %d' % (n_subsets, subset_size, n))
+    out = np.empty((n_subsets, subset_size), np.int32)
+    for s in range(n_subsets):
+        out[s] = np.random.RandomState([int(seed) & 0x7fffffff, int(which), s]).permutation(n)[:subset_size]
+    return out
+
+
+def _psd_eigenvalues(lam):
+    """Eigenvalues of a positive semi-definite matrix as computed: those below D eps max(lambda) are rounding of the
+    null space (fewer rows than dimensions) and count as zero, so that their square roots -- sqrt(eps) each, and of
+    either sign before the clipping -- do not reach the result."""
+    lam = np.maximum(lam, 0.0)
+    if lam.size:
+        lam[lam < len(lam) * np.finfo(np.float64).eps * lam.max()] = 0.0
+    return lam
+
+
+def frechet_from_moments(n1, sum1, second1, n2, sum2, second2):
+    """The Frechet distance |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) between the Gaussians fitted to two sets,
+    from their row counts, column sums (D,) and X^T X (D, D): float64 numpy on the host, O(D^3) whatever the set size.
+    Means and covariances with ddof = 1.  tr (S1 S2)^(1/2) is the sum of sqrt(max(lambda, 0)) over the eigenvalues of the
+    symmetric S1^(1/2) S2 S1^(1/2), which has the spectrum of S1 S2: two ``numpy.linalg.eigh`` calls, no complex
+    arithmetic, and rank-deficient covariances (fewer rows than dimensions) give a finite value.  NaN below 2 rows."""
+    n1, n2 = int(n1), int(n2)
+    if n1 < 2 or n2 < 2:
+        return float('nan')
+    mu, cov = [], []
+    for n, s, q in ((n1, sum1, second1), (n2, sum2, second2)):
+        s, q = np.asarray(s, np.float64).reshape(-1), np.asarray(q, np.float64)
+        m = s / n
+        mu.append(m)
+        cov.append((q.reshape(len(s), len(s)) - n * np.outer(m, m)) / (n - 1))
+    lam, Q = np.linalg.eigh((cov[0] + cov[0].T) * 0.5)
+    root = (Q * np.sqrt(_psd_eigenvalues(lam))) @ Q.T                    # the symmetric square root of S1
+    M = root @ cov[1] @ root
+    lam = _psd_eigenvalues(np.linalg.eigvalsh((M + M.T) * 0.5))
+    d = mu[0] - mu[1]
+    return float(d @ d + np.trace(cov[0]) + np.trace(cov[1]) - 2.0 * np.sqrt(lam).sum())
+
+
+VGG_SLICE_CHANNELS = (64, 128, 256, 512, 512)
+
+
+class FeatureDistance(object):
+    """Streams two sets into feature-space descriptors on the device and gives KID and the Frechet distance between them
+    (include/him.h "Feature-space set metrics").  ``add(fake, real)`` runs a frozen ``Vgg19`` (the one given, e.g.
+    ``model.criterionVGG.vgg``; otherwise one with the build's seeded synthetic weights is made on first use) without
+    autograd, one image per pass so that a row does not depend on the batching, and writes the plane means of the slices
+    ``layers`` (0 = relu1_1 .. 4 = relu5_1, concatenated) into rows of geometrically grown device buffers; ``add_features`` takes ready-made (n, D) fp32 device rows of any extractor
+    instead, and there the two sets may differ in size.  Every new row is folded into float64 moment accumulators as it
+    arrives.  The Frechet distance is called ``frechet``, not FID: the features are not Inception's."""
+
+    def __init__(self, layers=(4,), n_subsets=100, subset_size=1000, seed=0, vgg=None):
+        self.layers = tuple(int(l) for l in layers)
+        if not self.layers or any(l < 0 or l > 4 for l in self.layers):
+            raise ValueError('feature_distances: layers %r, each one of 0..4' % (layers,))
+        self.n_subsets, self.subset_size, self.seed, self.vgg = int(n_subsets), int(subset_size), int(seed), vgg
+        if self.n_subsets < 1 or self.subset_size < 2:
+            raise ValueError('feature_distances: n_subsets %d (>= 1), subset_size %d (>= 2)' % (self.n_subsets, self.subset_size))
+        self.D = None
+        self._rows, self._n, self._sum, self._second = [None, None], [0, 0], [None, None], [None, None]
+
+    def _reserve(self, which, n, D, dev):
+        if self.D is None:
+            self.D = int(D)
+            for w in (0, 1):
+                self._sum[w], self._second[w] = ops.feat_moment_buffers(self.D, dev)
+        elif self.D != int(D):
+            raise ValueError('feature_distances: rows of %d features after rows of %d' % (D, self.D))
+        buf, need = self._rows[which], self._n[which] + n
+        if buf is None or buf.shape[0] < need:
+            with torch.cuda.device(dev):
+                grown = torch.empty((max(need, 2 * (0 if buf is None else buf.shape[0])), self.D), dtype=torch.float32,
+                                    device=dev)
+            if buf is not None:
+                grown[:self._n[which]].copy_(buf[:self._n[which]])
+            buf = self._rows[which] = grown
+        return buf
+
+    def _fold(self, which, n):
+        ops.feat_moments(self._rows[which], self._n[which], n, self._sum[which], self._second[which])
+        self._n[which] += n
+
+    def add(self, fake, real):
+        fake, real = _image_pair(fake, real)
+        if fake.shape != real.shape or fake.shape[1] != 3 or min(fake.shape[-2:]) < 16:
+            raise ValueError('feature_distances: fake %s and real %s must be equal (B, 3, H, W) batches with '
+                             'min(H, W) >= 16' % (tuple(fake.shape), tuple(real.shape)))
+        if self.vgg is None:
+            from ..models.layer_util import Vgg19
+            from .. import synth
+            self.vgg = Vgg19()
+            self.vgg.load_state_dict(synth.init_state_dict(self.vgg.state_dict(), 3, 'vgg'))
+            self.vgg.to(fake.device)
+        B, D = fake.shape[0], sum(VGG_SLICE_CHANNELS[l] for l in self.layers)
+        for which, x in enumerate((fake, real)):
+            buf = self._reserve(which, B, D, x.device)
+            for b in range(B):
+                # one image per pass: the convolution kernels are chosen by shape, batch size included, so only this
+                # makes an image's row independent of the batch it arrived in
+                with torch.no_grad():
+                    maps = self.vgg(x[b:b + 1].contiguous())
+                c0 = 0
+                for l in self.layers:
+                    c0 = ops.feat_pool(maps[l], buf, self._n[which] + b, c0)
+            self._fold(which, B)
+        return self
+
+    def add_features(self, fake=None, real=None):
+        for which, rows in enumerate((fake, real)):
+            if rows is None:
+                continue
+            if not torch.is_tensor(rows) or not rows.is_cuda or rows.dtype != torch.float32 or rows.dim() != 2:
+                raise ValueError('feature_distances: features must be (n, D) fp32 device tensors')
+            if rows.shape[0] == 0:
+                continue
+            buf = self._reserve(which, rows.shape[0], rows.shape[1], rows.device)
+            buf[self._n[which]:self._n[which] + rows.shape[0]].copy_(rows.detach())
+            self._fold(which, rows.shape[0])
+        return self
+
+    @property
+    def n_features(self):
+        return (self._n[0], self._n[1])
+
+    def features(self, which):
+        """The (n, D) fp32 device rows of set ``which`` (0 generated, 1 real): a view of the buffer."""
+        return self._rows[which][:self._n[which]]
+
+    def kid_sums(self):
+        """``(sums (n_subsets, 3) float64, status, m)`` of ``ops.kid_sums`` on the seeded subsets."""
+        m = min(self.subset_size, self._n[0], self._n[1])
+        if m < 2:
+            raise ValueError('feature_distances: KID needs 2 rows per set, got %d and %d' % self.n_features)
+        dev = self._rows[0].device
+        ix = torch.from_numpy(kid_subsets(self.seed, 0, self._n[0], self.n_subsets, m)).to(dev)
+        iy = torch.from_numpy(kid_subsets(self.seed, 1, self._n[1], self.n_subsets, m)).to(dev)
+        out, status = ops.kid_sums(self.features(0), self.features(1), ix, iy, 0.0, 1.0)
+        return out, status, m
+
+    def kid(self):
+        """``(mean, std)`` float64 device scalars over the subsets of the unbiased MMD^2 estimate with the kernel
+        (x.y / D + 1)^3; ``subset_size`` is clipped to the smaller set.  ``std`` is the population deviation."""
+        s, _, m = self.kid_sums()
+        est = (s[:, 0] + s[:, 1]) / float(m * (m - 1)) - 2.0 * s[:, 2] / float(m * m)
+        return est.mean(), est.std(unbiased=False)
+
+    def frechet(self):
+        """The Frechet distance as a host float (one host synchronisation); NaN below 2 rows in either set."""
+        if min(self._n) < 2:
+            return float('nan')
+        return frechet_from_moments(self._n[0], self._sum[0].cpu().numpy(), self._second[0].cpu().numpy(),
+                                    self._n[1], self._sum[1].cpu().numpy(), self._second[1].cpu().numpy())
+
+
+def feature_distances(fake, real, **kw):
+    """KID and the Frechet distance between two whole image sets (N, 3, H, W) in VGG19 feature space:
+    ``dict(kid, kid_std, frechet, n_features)`` with the first two float64 device scalars; ``kw``: the arguments of
+    ``FeatureDistance``."""
+    fd = FeatureDistance(**kw).add(fake, real)
+    mean, std = fd.kid()
+    return OrderedDict([('kid', mean), ('kid_std', std), ('frechet', fd.frechet()), ('n_features', fd.n_features)])
+
+
+FEATURE_KEYS = ('kid', 'kid_std', 'frechet', 'n_features')
 SWD_KEYS = ('swd', 'swd_levels', 'swd_descriptors')
 BOUNDARY_KEYS = ('boundary_f1', 'per_class_boundary_f1', 'boundary_assd', 'mask_boundary_f1', 'mask_hausdorff')
 BAND_KEYS = ('band_mean_iou',)
@@ -346,7 +518,8 @@ class Evaluator(object):
     ``reconstruct`` and ``JointInference.gen_layout`` / ``gen_image`` return (a tensor, their dict, or their tuple, whose
     last entry is the generated tensor).  Nothing crosses to the host before ``summary()``."""
 
-    def __init__(self, label_nc, data_range=255., as_bytes=True, boundary_tolerance=None, band_radius=None, swd=None):
+    def __init__(self, label_nc, data_range=255., as_bytes=True, boundary_tolerance=None, band_radius=None, swd=None,
+                 features=None):
         self.label_nc, self.data_range, self.as_bytes = int(label_nc), float(data_range), bool(as_bytes)
         self._image, self._conf, self._mask, self._layouts = [], None, [], 0
         # opt-in contour measures: the tolerance of the boundary F-score in pixels, the radius of the trimap band
@@ -355,6 +528,9 @@ class Evaluator(object):
         self._bcounts, self._bsumd, self._mask_boundary, self._band = None, None, [], None
         # opt-in set-level measure: True, or a dict of n_patches, n_dirs, levels, seed, same_positions
         self._swd = None if swd is None or swd is False else SlicedWasserstein(**({} if swd is True else dict(swd)))
+        # opt-in feature-space measures: True, or a dict of layers, n_subsets, subset_size, seed, vgg
+        self._features = None if features is None or features is False else \
+            FeatureDistance(**({} if features is True else dict(features)))
 
     def add_image(self, fake, real, box=None):
         fake = _labels(fake, ('fake_image',))
@@ -362,6 +538,8 @@ class Evaluator(object):
         self._image.append(sums.sum(1))                               # (B, 5): channels pooled
         if self._swd is not None:
             self._swd.add(fake, real)                                 # whole images, as the tensors stand
+        if self._features is not None:
+            self._features.add(fake, real)
         return self
 
     def add_layout(self, pred, gt, mask=None):
@@ -432,6 +610,12 @@ class Evaluator(object):
             if self._swd.n_descriptors:
                 lv = self._swd.distances().cpu().numpy() * 1e3           # as the paper reports them
                 out.update(swd=float(lv.mean()), swd_levels=[float(v) for v in lv])
+        if self._features is not None:
+            n = self._features.n_features
+            out.update(kid=nan, kid_std=nan, frechet=nan, n_features=int(n[0]))         # rows per set
+            if min(n) >= 2:
+                mean, std = self._features.kid()
+                out.update(kid=float(mean.item()), kid_std=float(std.item()), frechet=self._features.frechet())
         return out
 
     def write_json(self, path):
