@@ -1048,9 +1048,37 @@ int him_swd_distance(const float* a, long long Na, const float* b, long long Nb,
  * the word) and makes the three sums of its subset NaN; other subsets are unaffected.  ws: him_kid_sums_ws(n_subsets, m)
  * bytes, 8-byte aligned.  Refused: m outside 2..65536, n_subsets outside 1..65535, D outside 1..2^20, nx or ny outside
  * 1..2^31 - 1, a negative or non-finite gamma, a non-finite coef0, a short workspace.
+ *
+ * k-nearest-neighbour manifold estimates (improved precision / recall, Kynkaanniemi et al. 2019; density / coverage,
+ * Naeem et al. 2020).  d2(a, b) is the squared Euclidean distance of two fp32 rows in the Gram form
+ * |a|^2 + |b|^2 - 2 a.b: operands widened to fp64 on load (every product exact), the dot products on
+ * v_mfma_f64_16x16x4_f64 (k ascending in groups of sixteen columns), the norms once per row in fp64, the result clamped
+ * at 0.  Both entries use the same arithmetic; neither stores the matrix of pairs.  Neither the row counts nor D need be
+ * a multiple of a tile; nothing is read past a row or past the last row.
+ *
+ * him_knn_radii: x (n, D) fp32; radii2[i], float64, = the k-th smallest d2(x_i, x_j) over j != i.  Self is excluded by
+ * position, not by value: a duplicate row is a neighbour at distance 0.  A workgroup owns 64 rows and a chunk of the
+ * columns and keeps, per row, the smallest values in a sorted register list; its first k go to ws, and a second launch
+ * merges a row's partial lists in chunk order.  The k smallest values of a set do not depend on the order they are met
+ * in, and there are no floating-point atomics: two runs give identical bits.  1 <= k <= HIM_KNN_MAX_K, k < n <=
+ * 2^31 - 1, 1 <= D <= HIM_FEAT_MAX_DIM.  ws: him_knn_radii_ws(n, D, k) bytes, 8-byte aligned (the norms and at most
+ * sixteen partial lists per row; 0 for a refused shape).
+ *
+ * him_knn_membership: q (nq, D) and r (nr, D) fp32, radii2 (nr) float64 -- the radii of the REFERENCE rows r.  With
+ *   I[j][i] = [ d2(q_j, r_i) <= radii2[i] ]      row_count[j] = sum_i I[j][i]      col_count[i] = sum_j I[j][i],
+ * int32; the call itself clears both (integer atomics add the non-zero tile sums: exact and order-free).  Either count
+ * pointer may be NULL to skip it, not both.  ws: him_knn_membership_ws(nq, nr, D) bytes, 8-byte aligned.
+ *
+ * A row with a non-finite feature sets HIM_KNN_NONFINITE in the int32 status[0] (atomic or; the caller zeroes the word).
+ * Every distance to or from it is NaN, which passes no comparison: it is nobody's neighbour, it lies within no radius
+ * and nothing lies within its own, which is NaN.  The other rows are unaffected; one with fewer than k finite
+ * neighbours has the radius +inf.  Refused: k, n, nq, nr or D outside the limits above, a NULL or misaligned x, q, r,
+ * radii2, status or ws, a short ws_bytes.
  * ------------------------------------------------------------------------------------------- */
 #define HIM_FEAT_MAX_DIM 4096
 #define HIM_KID_BAD_INDEX 1
+#define HIM_KNN_MAX_K 16
+#define HIM_KNN_NONFINITE 1
 int him_feat_pool(const float* x, int B, int C, int h, int w, float* feat, long long capacity, long long row0, int D, int c0,
                   void* stream);
 size_t him_feat_moments_ws(long long n, int D);
@@ -1059,6 +1087,12 @@ int him_feat_moments(const float* feat, long long row0, long long n, int D, doub
 size_t him_kid_sums_ws(int n_subsets, int m);
 int him_kid_sums(const float* x, long long nx, const float* y, long long ny, int D, const int* ix, const int* iy, int n_subsets,
                  int m, double gamma, double coef0, double* out, int* status, void* ws, size_t ws_bytes, void* stream);
+size_t him_knn_radii_ws(long long n, int D, int k);
+int him_knn_radii(const float* x, long long n, int D, int k, double* radii2, int* status, void* ws, size_t ws_bytes,
+                  void* stream);
+size_t him_knn_membership_ws(long long nq, long long nr, int D);
+int him_knn_membership(const float* q, long long nq, const float* r, long long nr, int D, const double* radii2, int* row_count,
+                       int* col_count, int* status, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

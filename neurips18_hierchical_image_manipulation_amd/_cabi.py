@@ -172,6 +172,10 @@ _SIGS = {
     'him_kid_sums_ws': (c_size_t, [c_int, c_int]),
     'him_kid_sums': (c_int, [P, C.c_longlong, P, C.c_longlong, c_int, P, P, c_int, c_int, C.c_double, C.c_double, P, P, P,
                              c_size_t, P]),
+    'him_knn_radii_ws': (c_size_t, [C.c_longlong, c_int, c_int]),
+    'him_knn_radii': (c_int, [P, C.c_longlong, c_int, c_int, P, P, P, c_size_t, P]),
+    'him_knn_membership_ws': (c_size_t, [C.c_longlong, C.c_longlong, c_int]),
+    'him_knn_membership': (c_int, [P, C.c_longlong, P, C.c_longlong, c_int, P, P, P, P, P, c_size_t, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

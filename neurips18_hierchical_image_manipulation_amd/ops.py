@@ -3131,3 +3131,63 @@ def kid_sums(x, y, ix, iy, gamma=0.0, coef0=1.0, status=None):
         lib.him_kid_sums(_p(x), x.shape[0], _p(y), y.shape[0], x.shape[1], _p(ix), _p(iy), n_subsets, m, gamma, coef0,
                          _p(out), _p(status), _p(ws), ws.numel() * 8, _stream())
     return out, status
+
+
+# -- k-nearest-neighbour manifold estimates: radii and membership counts (include/him.h, him_knn_radii / him_knn_membership)
+KNN_MAX_K, KNN_NONFINITE = 16, 1
+
+
+def _knn_status(status, device, what):
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    if not torch.is_tensor(status) or status.dtype != torch.int32 or not status.is_cuda or status.device != device:
+        raise ValueError('%s: status must be an int32 device tensor on the device of the rows' % what)
+    return status
+
+
+def knn_radii(x, k, status=None):
+    """``(radii2, status)``: ``radii2[i]``, float64, is the k-th smallest squared Euclidean distance from row i of the
+    fp32 device matrix ``x`` (n, D) to its other rows (self excluded by position: a duplicate row is a neighbour at
+    distance 0).  Gram form with exact products on the fp64 matrix instruction; the matrix of pairs is never stored;
+    identical bits from run to run.  A row with a non-finite feature sets KNN_NONFINITE in the int32 ``status[0]``, has
+    the radius NaN and is nobody's neighbour.  ``1 <= k <= KNN_MAX_K``, ``k < n``, ``D <= FEAT_MAX_DIM``.  Current
+    stream, no host synchronisation, no autograd; the workspace is cached per shape and device."""
+    x = _feat_matrix(x, 'knn_radii: x')
+    n, D, k = x.shape[0], x.shape[1], int(k)
+    if k < 1 or k > KNN_MAX_K or n <= k or D > FEAT_MAX_DIM:
+        raise ValueError('knn_radii: k %d (1..%d), x %s (more than k rows, at most %d columns)'
+                         % (k, KNN_MAX_K, tuple(x.shape), FEAT_MAX_DIM))
+    status = _knn_status(status, x.device, 'knn_radii')
+    with torch.cuda.device(x.device):
+        need = int(lib.him_knn_radii_ws(n, D, k))
+        ws = _swd_ws(('knn_radii', n, k), need, x.device)
+        radii2 = torch.empty(n, dtype=torch.float64, device=x.device)
+        lib.him_knn_radii(_p(x), n, D, k, _p(radii2), _p(status), _p(ws), ws.numel() * 8, _stream())
+    return radii2, status
+
+
+def knn_membership(q, ref, radii2, want_cols=True, status=None):
+    """``(row_count, col_count, status)`` of the indicator ``I[j, i] = d2(q_j, ref_i) <= radii2[i]`` between the fp32
+    device matrices ``q`` (nq, D) and ``ref`` (nr, D), ``radii2`` (nr,) float64 being the radii of the REFERENCE rows
+    (``knn_radii(ref, k)``): ``row_count[j] = sum_i I[j, i]`` (nq,) and ``col_count[i] = sum_j I[j, i]`` (nr,), int32;
+    ``col_count`` is None without ``want_cols``.  The arithmetic of ``knn_radii``; the indicator is never stored.  A
+    non-finite row sets KNN_NONFINITE in ``status[0]`` and takes part in no true comparison.  Current stream, no host
+    synchronisation, no autograd."""
+    q, ref = _feat_matrix(q, 'knn_membership: q'), _feat_matrix(ref, 'knn_membership: ref')
+    if ref.device != q.device or ref.shape[1] != q.shape[1] or q.shape[0] < 1 or ref.shape[0] < 1 \
+            or q.shape[1] > FEAT_MAX_DIM:
+        raise ValueError('knn_membership: q %s and ref %s must be non-empty, of one row length (at most %d) and on one '
+                         'device' % (tuple(q.shape), tuple(ref.shape), FEAT_MAX_DIM))
+    nq, nr, D = q.shape[0], ref.shape[0], q.shape[1]
+    if not torch.is_tensor(radii2) or radii2.dtype != torch.float64 or tuple(radii2.shape) != (nr,) \
+            or not radii2.is_contiguous() or radii2.device != q.device:
+        raise ValueError('knn_membership: radii2 must be a contiguous (%d,) float64 tensor on the device of q' % nr)
+    status = _knn_status(status, q.device, 'knn_membership')
+    with torch.cuda.device(q.device):
+        need = int(lib.him_knn_membership_ws(nq, nr, D))
+        ws = _swd_ws(('knn_member', nq, nr), need, q.device)
+        row_count = torch.empty(nq, dtype=torch.int32, device=q.device)
+        col_count = torch.empty(nr, dtype=torch.int32, device=q.device) if want_cols else None
+        lib.him_knn_membership(_p(q), nq, _p(ref), nr, D, _p(radii2.detach()), _p(row_count), _p(col_count), _p(status),
+                               _p(ws), ws.numel() * 8, _stream())
+    return row_count, col_count, status

@@ -391,8 +391,12 @@ class FeatureDistance(object):
     instead, and there the two sets may differ in size.  Every new row is folded into float64 moment accumulators as it
     arrives.  The Frechet distance is called ``frechet``, not FID: the features are not Inception's."""
 
-    def __init__(self, layers=(4,), n_subsets=100, subset_size=1000, seed=0, vgg=None):
+    def __init__(self, layers=(4,), n_subsets=100, subset_size=1000, seed=0, vgg=None, nearest_k=None):
         self.layers = tuple(int(l) for l in layers)
+        # opt-in: the k of ``prdc()`` (precision, recall, density, coverage by k-nearest neighbours)
+        self.nearest_k = None if nearest_k is None else int(nearest_k)
+        if self.nearest_k is not None and not 1 <= self.nearest_k <= ops.KNN_MAX_K:
+            raise ValueError('feature_distances: nearest_k %d outside 1..%d' % (self.nearest_k, ops.KNN_MAX_K))
         if not self.layers or any(l < 0 or l > 4 for l in self.layers):
             raise ValueError('feature_distances: layers %r, each one of 0..4' % (layers,))
         self.n_subsets, self.subset_size, self.seed, self.vgg = int(n_subsets), int(subset_size), int(seed), vgg
@@ -493,6 +497,66 @@ class FeatureDistance(object):
         return frechet_from_moments(self._n[0], self._sum[0].cpu().numpy(), self._second[0].cpu().numpy(),
                                     self._n[1], self._sum[1].cpu().numpy(), self._second[1].cpu().numpy())
 
+    def prdc_counts(self, nearest_k=None):
+        """``(k, row_fake_in_real, col_real_covered, row_real_in_fake, status)``: the int32 device counts of
+        ``ops.knn_membership`` of the generated rows against the real rows' k-th-neighbour radii (rows and columns) and of
+        the real rows against the generated rows' radii (rows); two radii calls and two membership calls."""
+        k = _nearest_k(self.nearest_k if nearest_k is None else nearest_k)
+        if min(self._n) <= k:
+            raise ValueError('feature_distances: precision / recall with k = %d need more than k rows per set, got %d and %d'
+                             % ((k,) + self.n_features))
+        fake, real = self.features(0), self.features(1)
+        r_real, status = ops.knn_radii(real, k)
+        r_fake, _ = ops.knn_radii(fake, k, status)
+        row_fr, col_r, _ = ops.knn_membership(fake, real, r_real, True, status)
+        row_rf, _, _ = ops.knn_membership(real, fake, r_fake, False, status)
+        return k, row_fr, col_r, row_rf, status
+
+    def prdc(self, nearest_k=None):
+        """``OrderedDict(precision, recall, density, coverage)`` of float64 device scalars on the rows held so far, with
+        ``nearest_k`` neighbours (default: the constructor's, else 5).  The generated set is tested against the real
+        rows' radii for precision, density and coverage, the real set against the generated rows' radii for recall.  All
+        four are NaN when either set has at most k rows."""
+        k = _nearest_k(self.nearest_k if nearest_k is None else nearest_k)
+        if min(self._n) <= k:
+            dev = self._rows[0].device if self._rows[0] is not None else None
+            return OrderedDict((key, torch.tensor(float('nan'), dtype=torch.float64, device=dev)) for key in PRDC_KEYS[:4])
+        return prdc_from_counts(*self.prdc_counts(k)[:4])
+
+
+def _nearest_k(k):
+    k = 5 if k is None else int(k)
+    if not 1 <= k <= ops.KNN_MAX_K:
+        raise ValueError('feature_distances: nearest_k %d outside 1..%d' % (k, ops.KNN_MAX_K))
+    return k
+
+
+def prdc_from_counts(k, row_fake_in_real, col_real_covered, row_real_in_fake):
+    """Precision, recall, density and coverage from the membership counts of ``ops.knn_membership``, as an
+    ``OrderedDict`` of float64 scalars on the device of the counts (no host synchronisation):
+    precision = the share of generated rows inside some real row's k-th-neighbour ball (``row_fake_in_real > 0``);
+    density = the number of such balls around a generated row, summed, over k times the generated rows;
+    coverage = the share of real rows whose ball holds a generated row (``col_real_covered > 0``);
+    recall = the share of real rows inside some generated row's ball (``row_real_in_fake > 0``)."""
+    k = int(k)
+    for t in (row_fake_in_real, col_real_covered, row_real_in_fake):
+        if not torch.is_tensor(t) or t.dim() != 1 or t.numel() < 1 or t.dtype.is_floating_point:
+            raise ValueError('prdc_from_counts: the counts must be non-empty one-dimensional integer tensors')
+    if k < 1:
+        raise ValueError('prdc_from_counts: k %d < 1' % k)
+    f64 = torch.float64
+    return OrderedDict([('precision', (row_fake_in_real > 0).to(f64).mean()),
+                        ('recall', (row_real_in_fake > 0).to(f64).mean()),
+                        ('density', row_fake_in_real.sum().to(f64) / float(k * row_fake_in_real.numel())),
+                        ('coverage', (col_real_covered > 0).to(f64).mean())])
+
+
+def feature_prdc(fake, real, nearest_k=5, **kw):
+    """Precision, recall, density and coverage between two whole image sets (N, 3, H, W) in VGG19 feature space:
+    ``OrderedDict(precision, recall, density, coverage)`` of float64 device scalars; ``kw``: the arguments of
+    ``FeatureDistance``."""
+    return FeatureDistance(nearest_k=nearest_k, **kw).add(fake, real).prdc()
+
 
 def feature_distances(fake, real, **kw):
     """KID and the Frechet distance between two whole image sets (N, 3, H, W) in VGG19 feature space:
@@ -504,6 +568,7 @@ def feature_distances(fake, real, **kw):
 
 
 FEATURE_KEYS = ('kid', 'kid_std', 'frechet', 'n_features')
+PRDC_KEYS = ('precision', 'recall', 'density', 'coverage', 'nearest_k')
 SWD_KEYS = ('swd', 'swd_levels', 'swd_descriptors')
 BOUNDARY_KEYS = ('boundary_f1', 'per_class_boundary_f1', 'boundary_assd', 'mask_boundary_f1', 'mask_hausdorff')
 BAND_KEYS = ('band_mean_iou',)
@@ -528,7 +593,8 @@ class Evaluator(object):
         self._bcounts, self._bsumd, self._mask_boundary, self._band = None, None, [], None
         # opt-in set-level measure: True, or a dict of n_patches, n_dirs, levels, seed, same_positions
         self._swd = None if swd is None or swd is False else SlicedWasserstein(**({} if swd is True else dict(swd)))
-        # opt-in feature-space measures: True, or a dict of layers, n_subsets, subset_size, seed, vgg
+        # opt-in feature-space measures: True, or a dict of layers, n_subsets, subset_size, seed, vgg, nearest_k (the last
+        # adds PRDC_KEYS to the summary)
         self._features = None if features is None or features is False else \
             FeatureDistance(**({} if features is True else dict(features)))
 
@@ -616,6 +682,9 @@ class Evaluator(object):
             if min(n) >= 2:
                 mean, std = self._features.kid()
                 out.update(kid=float(mean.item()), kid_std=float(std.item()), frechet=self._features.frechet())
+            if self._features.nearest_k is not None:
+                out.update((key, float(v.item())) for key, v in self._features.prdc().items())
+                out['nearest_k'] = int(self._features.nearest_k)
         return out
 
     def write_json(self, path):
