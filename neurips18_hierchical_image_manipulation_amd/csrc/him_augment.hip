@@ -186,20 +186,6 @@ __global__ __launch_bounds__(256) void da_apply_kernel(const float* __restrict__
   }
 }
 
-__device__ __forceinline__ double da_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// fixed tree over the 256 threads; valid in thread 0.  `sh` holds 4 doubles.
-__device__ __forceinline__ double da_block_sum(double v, double* sh) {
-  v = da_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // part[b * nchunk + j] = sum of chunk j of sample b's three image channels.  Forward: every element.  Backward: the
 // elements of dout that the forward pass routed somewhere (source inside the plane, not cut).  A sample whose row has no
 // colour bit is not read: its partials are zero.
@@ -249,7 +235,7 @@ __global__ __launch_bounds__(256) void da_partial_kernel(const float* __restrict
         a3 += (double)v[3];
       }
     }
-    const double s = da_block_sum((a0 + a1) + (a2 + a3), sh);
+    const double s = block_sum_f64((a0 + a1) + (a2 + a3), sh);
     if (threadIdx.x == 0) part[w] = s;
   }
 }
@@ -260,7 +246,7 @@ __global__ __launch_bounds__(256) void da_finish_kernel(const double* __restrict
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     double s = 0.0;
     for (int j = threadIdx.x; j < nchunk; j += 256) s += part[(size_t)b * nchunk + j];
-    s = da_block_sum(s, sh);
+    s = block_sum_f64(s, sh);
     if (threadIdx.x == 0) sums[b] = s;
   }
 }

@@ -77,12 +77,6 @@ __device__ __forceinline__ void ccl_union(int* P, int a, int b) {
   }
 }
 
-__device__ __forceinline__ int ccl_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---- 1: tile pass.  parent / area of every pixel of the plane are written here, so the workspace needs no clearing.
 template <typename T>
 __global__ __launch_bounds__(256) void ccl_tile_kernel(const T* __restrict__ cls, int H, int W, int tilesX, int tilesPer,
@@ -255,7 +249,7 @@ __global__ __launch_bounds__(256) void ccl_count_kernel(const int* __restrict__ 
     int n = 0;
 #pragma unroll
     for (int k = 0; k < CCL_PER; ++k) n += ccl_kept(parent, area, pb, l0 + k * 256 + threadIdx.x, HW, min_area);
-    n = ccl_wave_sum(n);
+    n = wave_sum_i32(n);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = n;
     __syncthreads();

@@ -66,12 +66,6 @@ __global__ void edt_status_kernel(const int* __restrict__ jobs, int B, int K, in
   }
 }
 
-__device__ __forceinline__ int edt_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void edt_row_kernel(const T* __restrict__ src, const int* __restrict__ jobs, int B, int H,
                                                       int W, int K, short* __restrict__ g, int* __restrict__ status) {
@@ -112,7 +106,7 @@ __global__ __launch_bounds__(256) void edt_row_kernel(const T* __restrict__ src,
       if (x < W) lft[x] = (short)m;
       __syncthreads();
     }
-    cnt = edt_wave_sum(cnt);
+    cnt = wave_sum_i32(cnt);
     if (lane == 0 && cnt) atomicAdd(&status[2 * k], cnt);
     // walking left: the nearest seed at or right of x; every thread reads back the lft cells it wrote itself
     carry = EDT_BIG;

@@ -3,47 +3,25 @@
 // polynomial-kernel MMD (KID).  The two arithmetic-heavy reductions run on the fp64 matrix instruction
 // v_mfma_f64_16x16x4_f64 with fp32 operands widened on load: a product of two fp32 values is exact in fp64, so only the
 // summation rounds.  No floating-point atomics; every sum that crosses threads goes through a fixed butterfly over the
-// lanes of a wave, a fixed sum over the four waves, and (KID) one partial per tile in the workspace that a second launch
-// adds in tile order: results are bit-identical from run to run.
-//
-// Fragment layout of v_mfma_f64_16x16x4_f64 (one f64 per lane for A and B, four per lane for C/D):
-//   A[m][k]: m = lane & 15, k = lane >> 4        B[k][n]: k = lane >> 4, n = lane & 15
-//   C/D register q: column n = lane & 15, row m = (lane >> 4) + 4 q      (NOT the f32 map 4 (lane >> 4) + q)
+// lanes of a wave, a fixed sum over the four waves (block_sum_f64, him_common.h), and (KID) one partial per tile in the
+// workspace that a second launch adds in tile order: results are bit-identical from run to run.  The fragment layout of
+// the instruction is written down in him_mfma_f64.h.
 //
 // him_feat_pool     a workgroup per (image, channel) plane, thread t adds elements t, t + 256, ... in double.
 // him_feat_moments  a wave per 16 x 16 tile of the upper triangle of X^T X; k walks the rows four at a time; the tile is
 //                   added to `second` and to its mirror image, the diagonal tile only from its own upper triangle.
-// him_kid_sums      a workgroup per 64 x 64 tile of pairs, a wave per 32 x 32 (2 x 2 accumulators).  A lane loads four
-//                   consecutive columns of its row with one 16-byte load and feeds them to four instructions: both
-//                   operands permute k the same way, so every instruction still multiplies matching columns.  The cube
-//                   and the masks (diagonal by position, ragged edge) run on the accumulators; the Gram matrix is never
-//                   stored.  Tiles below the diagonal of the xx and yy blocks are skipped and those above count twice.
+// him_kid_sums      a workgroup per 64 x 64 tile of pairs, a wave per 32 x 32 (gram_tile_32x32, him_mfma_f64.h).  The
+//                   cube and the masks (diagonal by position, ragged edge) run on the accumulators; the Gram matrix is
+//                   never stored.  Tiles below the diagonal of the xx and yy blocks are skipped, those above count twice.
 #include <math.h>
 
 #include "him_common.h"
+#include "him_mfma_f64.h"
 
 namespace him {
 
-typedef double feat_d4 __attribute__((ext_vector_type(4)));
-
 #define KID_TILE 64
 #define KID_MAX_M 65536
-
-// butterfly over the 64 lanes: a + b is commutative, so every lane ends with the same bits
-__device__ __forceinline__ double feat_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// 256-thread workgroups; the result is valid in every thread.  `sh` holds 4 doubles.
-__device__ __forceinline__ double feat_block_sum(double v, double* sh) {
-  v = feat_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 
 // ---- pool -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void feat_pool_kernel(const float* __restrict__ x, long long planes, int C, long long hw,
@@ -53,7 +31,7 @@ __global__ __launch_bounds__(256) void feat_pool_kernel(const float* __restrict_
     const float* in = x + (size_t)p * hw;
     double acc = 0.0;
     for (long long i = threadIdx.x; i < hw; i += 256) acc += (double)in[i];
-    const double r = feat_block_sum(acc, sh);
+    const double r = block_sum_f64(acc, sh);
     if (threadIdx.x == 0) {
       const long long b = p / C, c = p - b * C;
       feat[(size_t)(row0 + b) * D + c0 + c] = (float)(r / (double)hw);
@@ -83,7 +61,7 @@ __global__ __launch_bounds__(256) void feat_second_kernel(const float* __restric
   const int r = lane >> 4, c = lane & 15;
   const int ca = ta * 16 + c, cb = tb * 16 + c;
   const bool oka = ca < D, okb = cb < D;
-  feat_d4 acc = {0.0, 0.0, 0.0, 0.0};
+  mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
   for (long long i0 = 0; i0 < n; i0 += 4) {
     const long long i = i0 + r;
     double a = 0.0, b = 0.0;                              // padding lives in registers: nothing is read past a row
@@ -106,16 +84,6 @@ __global__ __launch_bounds__(256) void feat_second_kernel(const float* __restric
 }
 
 // ---- KID --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void kid_load4(const float* __restrict__ row, int k, int D, bool vec, double* o) {
-  if (vec && k < D) {                                     // vec: D % 4 == 0 and 16-byte aligned rows, so k + 3 < D
-    const float4 v = *(const float4*)(row + k);
-    o[0] = (double)v.x, o[1] = (double)v.y, o[2] = (double)v.z, o[3] = (double)v.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = k + j < D ? (double)row[k + j] : 0.0;
-  }
-}
-
 // the row an index of the table stands for; an index outside the matrix is replaced (and reported by the second launch)
 __device__ __forceinline__ const float* kid_row(const float* __restrict__ base, long long n_rows, const int* __restrict__ idx,
                                                 int pos, int m, int D) {
@@ -148,23 +116,8 @@ __global__ __launch_bounds__(256) void kid_tile_kernel(const float* __restrict__
     pa[u] = kid_row(am, na, ia, i_base + u * 16 + c, m, D);
     pb[u] = kid_row(bm, nb, ib, j_base + u * 16 + c, m, D);
   }
-  feat_d4 acc[2][2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < 2; ++v) acc[u][v] = (feat_d4){0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < D; k0 += 16) {
-    const int k = k0 + 4 * g;                             // instruction j multiplies the columns k0 + 4 g' + j, g' = 0..3
-    double a[2][4], b[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) kid_load4(pa[u], k, D, vec != 0, a[u]), kid_load4(pb[u], k, D, vec != 0, b[u]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][j], b[v][j], acc[u][v], 0, 0, 0);
-  }
+  mfma_d4 acc[2][2];
+  gram_tile_32x32(pa[0], pa[1], pb[0], pb[1], D, vec, g, acc);
   double part = 0.0;
 #pragma unroll
   for (int u = 0; u < 2; ++u)
@@ -178,7 +131,7 @@ __global__ __launch_bounds__(256) void kid_tile_kernel(const float* __restrict__
           part += t * t * t;
         }
       }
-  const double r = feat_block_sum(part, sh);
+  const double r = block_sum_f64(part, sh);
   if (threadIdx.x == 0) ws[((size_t)s * 3 + kind) * T * T + blockIdx.x] = (kind < 2 && tj > ti) ? 2.0 * r : r;
 }
 
@@ -201,7 +154,7 @@ __global__ __launch_bounds__(256) void kid_reduce_kernel(const double* __restric
       const int ti = t / T, tj = t - ti * T;
       if (kind == 2 || tj >= ti) acc += part[t];
     }
-    const double r = feat_block_sum(acc, sh);
+    const double r = block_sum_f64(acc, sh);
     if (tid == 0) out[(size_t)s * 3 + kind] = bad ? (double)NAN : r;
   }
   if (bad && tid == 0) atomicOr(status, HIM_KID_BAD_INDEX);
@@ -272,7 +225,7 @@ int him_kid_sums(const float* x, long long nx, const float* y, long long ny, int
   const size_t need = kid_ws_bytes(n_subsets, m);
   if (ws_bytes < need) return fail(HIM_E_WORKSPACE, "kid_sums: workspace %zu < %zu bytes", ws_bytes, need);
   const int T = cdiv(m, KID_TILE);
-  const int vec = (D % 4 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0) ? 1 : 0;
+  const int vec = gram_vec_ok(D, x, y);
   hipLaunchKernelGGL(kid_tile_kernel, dim3((unsigned)(T * T), 3, (unsigned)n_subsets), dim3(256), 0, ST, x, nx, y, ny, D, ix, iy,
                      m, T, gamma == 0.0 ? 1.0 / (double)D : gamma, coef0, vec, (double*)ws);
   hipLaunchKernelGGL(kid_reduce_kernel, dim3((unsigned)n_subsets), dim3(256), 0, ST, (const double*)ws, ix, iy, nx, ny, m, T, out,

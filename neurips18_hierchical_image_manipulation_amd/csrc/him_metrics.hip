@@ -43,12 +43,6 @@ __device__ __forceinline__ float met_map(float x, const MetParams& p) {
   return v;
 }
 
-__device__ __forceinline__ double met_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // the clipped box of sample b: origin (x0, y0), size (w, h); h <= 0 or w <= 0: empty
 __device__ __forceinline__ void met_region(const int* __restrict__ box, int b, int H, int W, int& x0, int& y0, int& w, int& h) {
   if (box == nullptr) {
@@ -160,9 +154,9 @@ __global__ __launch_bounds__(256) void image_metrics_tile_kernel(const float* __
       if (map_out != nullptr) map_out[((size_t)plane * (H - MET_HALO) + oy) * (W - MET_HALO) + ox] = s;
     }
   }
-  ss = met_wave_sum(ss);
-  sq = met_wave_sum(sq);
-  ab = met_wave_sum(ab);
+  ss = wave_sum_f64(ss);
+  sq = wave_sum_f64(sq);
+  ab = wave_sum_f64(ab);
   if (col == 0) red[0][rg] = ss, red[1][rg] = sq, red[2][rg] = ab;
   __syncthreads();
   if (tid < MET_PART) slot[tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);

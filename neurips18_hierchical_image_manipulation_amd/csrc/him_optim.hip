@@ -172,20 +172,6 @@ __global__ __launch_bounds__(256) void gs_plan_kernel(const long long* __restric
   if (t == 255) first[R] = sh[256] < cap ? sh[256] : cap;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// fixed tree over the 256 threads; the result is valid in thread 0.  `sh` holds >= 4 doubles.
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // finite: x * x is exact in double (24 x 24 bits) and the fma rounds the sum once; Inf / NaN: counted, adds nothing
 __device__ __forceinline__ void gs_acc(float x, double& acc, unsigned& bad) {
   if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) {

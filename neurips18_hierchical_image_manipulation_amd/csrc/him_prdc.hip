@@ -2,7 +2,7 @@
 // him_knn_membership): the all-pairs squared distances of descriptor rows in Gram form |a|^2 + |b|^2 - 2 a.b, the k-th
 // smallest per row, and the membership counts against per-row radii -- what improved precision / recall (Kynkaanniemi et
 // al. 2019) and density / coverage (Naeem et al. 2020) are made of.  The dot products run on v_mfma_f64_16x16x4_f64 with
-// fp32 operands widened on load (exact products, as in him_featdist.hip, whose fragment layout note applies: C/D register
+// fp32 operands widened on load (exact products; the tile and the fragment layout note are in him_mfma_f64.h: C/D register
 // q of a lane holds row (lane >> 4) + 4 q, column lane & 15); the n x n matrix is never stored.  No floating-point
 // atomics: the selection keeps VALUES, and the k smallest values of a multiset do not depend on the order they arrive in;
 // the counts are integers.  Results are bit-identical from run to run.
@@ -12,7 +12,7 @@
 //                     then NaN, and NaN passes neither the `<` of the selection nor the `<=` of the membership test.
 //                     The same launch clears the count the row owns (membership).
 // knn_radii_kernel    a workgroup per (block of 64 rows, chunk of column tiles); per 64 x 64 tile a wave computes 32 x 32
-//                     (2 x 2 accumulators, the loads of him_kid_sums), the distances go to LDS (row stride 68 doubles),
+//                     (gram_tile_32x32, as in him_kid_sums), the distances go to LDS (row stride 68 doubles),
 //                     and thread t -- row t >> 2, columns (t & 3) + 4 s -- pushes its 16 values through a sorted list of
 //                     the KL smallest kept in registers (KL = 4, 8 or 16 >= k; compare-exchange chain, static indices).
 //                     With that stride and interleave the 32 lanes of an LDS read group hit 32 different 8-byte slots.
@@ -25,10 +25,9 @@
 #include <math.h>
 
 #include "him_common.h"
+#include "him_mfma_f64.h"
 
 namespace him {
-
-typedef double knn_d4 __attribute__((ext_vector_type(4)));
 
 #define KNN_TILE 64
 #define KNN_LDS_STRIDE 68          // doubles per LDS row of the distance tile
@@ -50,8 +49,7 @@ __global__ __launch_bounds__(256) void knn_norm_kernel(const float* __restrict__
     bad |= (v - v == 0.f) ? 0 : 1;                        // inf - inf and NaN - NaN are NaN
     acc += (double)v * (double)v;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum_f64(acc);
   bad = __any(bad);
   if (lane == 0) {
     norm[i] = bad ? (double)NAN : acc;
@@ -60,26 +58,16 @@ __global__ __launch_bounds__(256) void knn_norm_kernel(const float* __restrict__
   }
 }
 
-// ---- the 64 x 64 Gram tile --------------------------------------------------------------------------------------------
-__device__ __forceinline__ void knn_load4(const float* __restrict__ row, int k, int D, bool vec, double* o) {
-  if (vec && k < D) {                                     // vec: D % 4 == 0 and 16-byte aligned rows, so k + 3 < D
-    const float4 v = *(const float4*)(row + k);
-    o[0] = (double)v.x, o[1] = (double)v.y, o[2] = (double)v.z, o[3] = (double)v.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = k + j < D ? (double)row[k + j] : 0.0;
-  }
-}
-
+// ---- the 64 x 64 Gram tile: rows by position ---------------------------------------------------------------------------
 // a position outside the matrix reads row 0 (and is masked by the caller): nothing is read past the last row
 __device__ __forceinline__ const float* knn_row(const float* __restrict__ base, int n, int pos, int D) {
   return base + (size_t)(pos < n ? pos : 0) * D;
 }
 
-// acc[u][v] = the 16 x 16 products of rows i_base + 16 u + .. of a with rows j_base + 16 v + .. of b (this wave's 32 x 32)
+// this wave's 32 x 32: acc[u][v] = the 16 x 16 products of rows i_base + 16 u + .. of a with rows j_base + 16 v + .. of b
 __device__ __forceinline__ void knn_gram(const float* __restrict__ a, int na, int i_base, const float* __restrict__ b, int nb,
-                                         int j_base, int D, bool vec, int lane, knn_d4 (&acc)[2][2]) {
-  const int g = lane >> 4, c = lane & 15;
+                                         int j_base, int D, bool vec, int lane, mfma_d4 (&acc)[2][2]) {
+  const int c = lane & 15;
   const float* pa[2];
   const float* pb[2];
 #pragma unroll
@@ -87,22 +75,7 @@ __device__ __forceinline__ void knn_gram(const float* __restrict__ a, int na, in
     pa[u] = knn_row(a, na, i_base + u * 16 + c, D);
     pb[u] = knn_row(b, nb, j_base + u * 16 + c, D);
   }
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < 2; ++v) acc[u][v] = (knn_d4){0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < D; k0 += 16) {
-    const int k = k0 + 4 * g;                             // instruction j multiplies the columns k0 + 4 g' + j, g' = 0..3
-    double av[2][4], bv[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) knn_load4(pa[u], k, D, vec, av[u]), knn_load4(pb[u], k, D, vec, bv[u]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][j], bv[v][j], acc[u][v], 0, 0, 0);
-  }
+  gram_tile_32x32(pa[0], pa[1], pb[0], pb[1], D, vec, lane >> 4, acc);
 }
 
 // |a|^2 + |b|^2 - 2 a.b clamped at 0; NaN (a non-finite row) stays NaN
@@ -151,7 +124,7 @@ __global__ __launch_bounds__(256) void knn_radii_kernel(const float* __restrict_
 
   for (int tj = t0; tj < t1; ++tj) {
     const int j_base = tj * KNN_TILE + lj_base;
-    knn_d4 acc[2][2];
+    mfma_d4 acc[2][2];
     knn_gram(x, n, i_base, x, n, j_base, D, vec != 0, lane, acc);
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
@@ -229,7 +202,7 @@ __global__ __launch_bounds__(256) void knn_member_kernel(const float* __restrict
     }
   for (int tj = blockIdx.y; tj < Tr; tj += gridDim.y) {
     const int j_base = tj * KNN_TILE + (wave & 1) * 32;
-    knn_d4 acc[2][2];
+    mfma_d4 acc[2][2];
     knn_gram(qm, nq, i_base, rm, nr, j_base, D, vec != 0, lane, acc);
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
@@ -305,7 +278,7 @@ int him_knn_radii(const float* x, long long n, int D, int k, double* radii2, int
   int chunk_tiles;
   const int n_chunks = knn_chunks(n, &chunk_tiles);
   const int T = cdiv(n, KNN_TILE), ni = (int)n;
-  const int vec = (D % 4 == 0 && (uintptr_t)x % 16 == 0) ? 1 : 0;
+  const int vec = gram_vec_ok(D, x, x);
   double* norm = (double*)ws;
   double* part = norm + n;
   hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, ST, x, ni, D, norm, (int*)nullptr, status);
@@ -339,7 +312,7 @@ int him_knn_membership(const float* q, long long nq, const float* r, long long n
   const size_t need = (size_t)(nq + nr) * sizeof(double);
   if (ws_bytes < need) return fail(HIM_E_WORKSPACE, "knn_membership: workspace ws_bytes %zu < %zu bytes", ws_bytes, need);
   const int Tq = cdiv(nq, KNN_TILE), Tr = cdiv(nr, KNN_TILE);
-  const int vec = (D % 4 == 0 && (uintptr_t)q % 16 == 0 && (uintptr_t)r % 16 == 0) ? 1 : 0;
+  const int vec = gram_vec_ok(D, q, r);
   double* qnorm = (double*)ws;
   double* rnorm = qnorm + nq;
   hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, ST, q, (int)nq, D, qnorm, row_count, status);

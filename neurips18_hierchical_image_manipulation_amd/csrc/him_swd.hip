@@ -180,8 +180,7 @@ __global__ __launch_bounds__(256) void swd_gather_kernel(const float* __restrict
       const double rn = swd_block_reduce<1>(mn[c], sh), rx = swd_block_reduce<2>(mx[c], sh);
       if (tid == 0) slot[c * SWD_NSTAT] = rs, slot[c * SWD_NSTAT + 1] = rq, slot[c * SWD_NSTAT + 2] = rn, slot[c * SWD_NSTAT + 3] = rx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) clamped += __shfl_xor(clamped, o, 64);
+    clamped = wave_sum_i32(clamped);
     __syncthreads();
     if ((tid & 63) == 0) shc[tid >> 6] = clamped;
     __syncthreads();
@@ -279,8 +278,7 @@ __global__ __launch_bounds__(256) void sort_chunks_kernel(const unsigned* __rest
     }
     s[i] = key;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nans += __shfl_xor(nans, o, 64);
+  nans = wave_sum_i32(nans);
   if ((tid & 63) == 0) shc[tid >> 6] = nans;
   __syncthreads();
   if (tid == 0) {
