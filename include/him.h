@@ -1094,6 +1094,65 @@ size_t him_knn_membership_ws(long long nq, long long nr, int D);
 int him_knn_membership(const float* q, long long nq, const float* r, long long nr, int D, const double* radii2, int* row_count,
                        int* col_count, int* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Panoptic matching (the reference ships no metric code; panoptic quality PQ = SQ x RQ of Kirillov et al., "Panoptic
+ * Segmentation", CVPR 2019): the instance-aware comparison of a predicted layout with the ground truth.  One call on
+ * `stream`, no host synchronisation, no allocation; integer counting throughout, results bit-identical from run to run.
+ * Each plane b of the batch is handled independently.
+ *   pred_seg, gt_seg: (B,H,W) segment ids, kind 0 uint8 / 1 int32 / 2 int64; accepted ids 0..65535 (the id domain of
+ *            him_inst_summary and of what him_label_instances writes).  Never written.
+ *   pred_cls, gt_cls: (B,H,W) classes, kind 0 uint8 / 1 int32 / 2 int64 / 3 fp32 holding integral values; accepted
+ *            0..n_class-1, 1 <= n_class <= 256.  Never written.
+ *   mask:    NULL, or fp32 (B,H,W).
+ *   Void:    a pixel is void where mask == 0, or where its ground-truth class equals `ignore` (-1: none; compared before
+ *            the range check, so it may be >= n_class).  A void pixel belongs to no ground-truth segment -- its
+ *            ground-truth id and class are not examined -- but it still belongs to its predicted segment.
+ *   Segment: the set of a plane's pixels with one id (ground truth: non-void pixels only); its class is the smallest
+ *            class value under it; classes that are not all equal set HIM_PQ_MIXED (informational, the plane is still
+ *            counted).  Segments are ranked per side in ascending id (np.unique's order).
+ *   Matching, in integers, of ground-truth segment g and predicted segment p: inter = |g n p|, void_p = |p n void|,
+ *            union = |g| + |p| - inter - void_p; they match iff their classes are equal and 2 * inter > union.  Such a
+ *            match is unique on both sides (csrc/him_panoptic.hip has the proof).
+ *   Counts per class: a matched pair adds 1 to tp of its class and (double)inter / (double)union to iou_sum; an
+ *            unmatched ground-truth segment adds 1 to fn; an unmatched predicted segment adds 1 to fp unless
+ *            2 * void_p > |p|.  No crowd regions.
+ *   counts:  int64 (n_class,3) = tp, fp, fn.   iou_sum: double (n_class).  accumulate != 0 adds into both (and into
+ *            status: the two counts are added, the flags or-ed); otherwise they are overwritten.  Each class has one
+ *            writer, which adds its IoU terms in a fixed order; no floating-point atomics.
+ *   matches: NULL, or int32 (B,max_segments,6): one row per ground-truth segment in rank order: id, class, area,
+ *            matched predicted id or -1, inter, union (0, 0 when unmatched).  Rows behind the plane's segment count are
+ *            not written.
+ *   status:  int32 (B,4): [ground-truth segments, predicted segments, flags, 0]; the counts are the true ones (of the
+ *            ids inside 0..65535), also past max_segments.  Flags: HIM_PQ_OVERFLOW (either side has more than
+ *            max_segments), HIM_PQ_ID_RANGE (an id outside 0..65535), HIM_PQ_CLS_RANGE (a class outside 0..n_class-1 or
+ *            a non-integral fp32), HIM_PQ_MIXED.  A plane with any of the first three adds nothing to counts or iou_sum,
+ *            its matches rows are unspecified and its HIM_PQ_MIXED bit is clear; the other planes are unaffected.
+ *            HIM_PQ_CCL is never set by the library: the caller's spare bit (util/metrics.py marks a plane whose
+ *            instance labelling reported a flag of its own).
+ *   ws:      him_panoptic_match_workspace(B, max_segments) bytes, 16-byte aligned, cleared by the call itself;
+ *            1 <= max_segments <= 4096 (a dense (max_segments + 1) x max_segments int32 pair table per plane, of which
+ *            a call touches (ground-truth segments + 1) x predicted segments).
+ * Nothing outside counts, iou_sum, matches, status and ws is ever written.  Seven launches: clear, segment pass (one
+ * integer atomic per run of equal ids into a table of 65536 ids per plane and side), rank pass (prefix sum of the present
+ * ids), clear of the pair table, pair pass (one atomic per run of equal pairs), match pass (a wave per ground-truth
+ * segment), reduce pass (a wave per class).  A lane reads 4 pixels of every plane per step, as one vector load where every
+ * base is 16-byte aligned and W % 4 == 0, element by element otherwise.  No cooperative launch, no workgroup waits for
+ * another.
+ * HIM_E_INVALID before any launch: a NULL required pointer, an unknown kind, B, H or W < 1, B > 65535,
+ * H * W > 2^31 - 1, n_class or max_segments out of range, ignore < -1, a plane not aligned to its element, a misaligned
+ * output or workspace; HIM_E_WORKSPACE for a short workspace (the query returns 0 for a refused shape).
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_PQ_OVERFLOW 1
+#define HIM_PQ_ID_RANGE 2
+#define HIM_PQ_CLS_RANGE 4
+#define HIM_PQ_MIXED 8
+#define HIM_PQ_CCL 16
+size_t him_panoptic_match_workspace(int B, int max_segments);
+int him_panoptic_match(const void* pred_seg, int pred_seg_kind, const void* pred_cls, int pred_cls_kind,
+                       const void* gt_seg, int gt_seg_kind, const void* gt_cls, int gt_cls_kind, const float* mask, int B,
+                       int H, int W, int n_class, int ignore, int max_segments, int accumulate, long long* counts,
+                       double* iou_sum, int* matches, int* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,8 @@ _SIGS = {
     'him_knn_radii': (c_int, [P, C.c_longlong, c_int, c_int, P, P, P, c_size_t, P]),
     'him_knn_membership_ws': (c_size_t, [C.c_longlong, C.c_longlong, c_int]),
     'him_knn_membership': (c_int, [P, C.c_longlong, P, C.c_longlong, c_int, P, P, P, P, P, c_size_t, P]),
+    'him_panoptic_match_workspace': (c_size_t, [c_int, c_int]),
+    'him_panoptic_match': (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P] + [c_int] * 7 + [P, P, P, P, P, c_size_t, P]),
     'him_masked_image': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'him_edges': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'him_masked_mean': (c_int, [P, P, P, P, c_int, c_int, P]),

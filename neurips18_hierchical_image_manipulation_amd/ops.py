@@ -2900,6 +2900,84 @@ def label_ids(pred, pred_kind):
     return ids
 
 
+# -- panoptic matching: segments, overlaps, unique matches, per-class tp / fp / fn (include/him.h "Panoptic matching") ---
+PQ_OVERFLOW, PQ_ID_RANGE, PQ_CLS_RANGE, PQ_MIXED, PQ_CCL = 1, 2, 4, 8, 16
+_SEG_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
+_PQ_WS = {}             # (B, max_segments, device index) -> workspace of him_panoptic_match
+
+
+def _pq_planes(t, what, kinds):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('panoptic_match: %s must be a device tensor' % what)
+    if t.dtype not in kinds:
+        raise ValueError('panoptic_match: %s is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in kinds)))
+    if t.dim() == 2:
+        t = t[None]
+    elif t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or 0 in t.shape:
+        raise ValueError('panoptic_match: %s must be (B, H, W), (B, 1, H, W) or (H, W), got %s' % (what, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def panoptic_match(pred_seg, pred_cls, gt_seg, gt_cls, n_class, *, mask=None, ignore=-1, max_segments=1024, out=None,
+                   want_matches=False):
+    """``(counts, iou_sum, status, matches or None)`` on the device: per class the int64 (n_class, 3) tp / fp / fn of the
+    predicted segments against the ground-truth ones (matched at IoU > 0.5 within a class, void taken out), the float64
+    (n_class,) sum of the matched IoUs, the int32 (B, 4) record [ground-truth segments, predicted segments, flag bits, 0]
+    and, with ``want_matches``, the int32 (B, max_segments, 6) rows id, class, area, matched predicted id or -1, inter,
+    union of every ground-truth segment.  ``*_seg``: uint8 / int32 / int64 ids 0..65535; ``*_cls``: uint8 / int32 / int64 /
+    integral fp32 classes; ``mask``: fp32, void where 0; ``ignore``: a ground-truth class that is void.  ``out``: the
+    (counts, iou_sum, status) triple an earlier call returned; the call then adds into it.  Current stream, no host
+    synchronisation.  The workspace is cached per (B, max_segments) and device: calls of one shape must be queued on one
+    stream at a time."""
+    pred_seg = _pq_planes(pred_seg, 'pred_seg', _SEG_KINDS)
+    pred_cls = _pq_planes(pred_cls, 'pred_cls', _PRED_KINDS)
+    gt_seg = _pq_planes(gt_seg, 'gt_seg', _SEG_KINDS)
+    gt_cls = _pq_planes(gt_cls, 'gt_cls', _PRED_KINDS)
+    B, H, W = pred_seg.shape
+    for what, t in (('pred_cls', pred_cls), ('gt_seg', gt_seg), ('gt_cls', gt_cls)):
+        if tuple(t.shape) != (B, H, W) or t.device != pred_seg.device:
+            raise ValueError('panoptic_match: pred_seg %s and %s %s differ' % (tuple(pred_seg.shape), what, tuple(t.shape)))
+    if mask is not None:
+        mask = _pq_planes(mask, 'mask', (torch.float32,))
+        if tuple(mask.shape) != (B, H, W) or mask.device != pred_seg.device:
+            raise ValueError('panoptic_match: mask %s does not fit pred_seg %s' % (tuple(mask.shape), (B, H, W)))
+    n_class, max_segments, ignore = int(n_class), int(max_segments), int(ignore)
+    if not 1 <= n_class <= 256:
+        raise ValueError('panoptic_match: n_class must be in 1..256, got %d' % n_class)
+    if not 1 <= max_segments <= 4096:
+        raise ValueError('panoptic_match: max_segments must be in 1..4096, got %d' % max_segments)
+    if ignore < -1 or H * W > 0x7fffffff or B > 65535:
+        raise ValueError('panoptic_match: ignore %d (-1 or a class), planes of %d x %d (at most 2^31 - 1 pixels), batch %d '
+                         '(at most 65535)' % (ignore, H, W, B))
+    dev = pred_seg.device
+    with torch.cuda.device(dev):
+        key = (B, max_segments, torch.cuda.current_device())
+        ws = _PQ_WS.get(key)
+        if ws is None:
+            nws = int(lib.him_panoptic_match_workspace(B, max_segments))
+            ws = _PQ_WS[key] = torch.empty((nws + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        if out is None:
+            counts = torch.empty((n_class, 3), dtype=torch.int64, device=dev)
+            iou_sum = torch.empty(n_class, dtype=torch.float64, device=dev)
+            status = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        else:
+            counts, iou_sum, status = out[:3]
+            ok = all(torch.is_tensor(t) and t.device == dev and t.is_contiguous() for t in (counts, iou_sum, status))
+            if not ok or counts.dtype != torch.int64 or tuple(counts.shape) != (n_class, 3) \
+                    or iou_sum.dtype != torch.float64 or tuple(iou_sum.shape) != (n_class,) \
+                    or status.dtype != torch.int32 or tuple(status.shape) != (B, 4):
+                raise ValueError('panoptic_match: out must be the (counts (%d, 3) int64, iou_sum (%d,) float64, status '
+                                 '(%d, 4) int32) triple of an earlier call' % (n_class, n_class, B))
+        matches = torch.empty((B, max_segments, 6), dtype=torch.int32, device=dev) if want_matches else None
+        lib.him_panoptic_match(_p(pred_seg), _SEG_KINDS[pred_seg.dtype], _p(pred_cls), _PRED_KINDS[pred_cls.dtype],
+                               _p(gt_seg), _SEG_KINDS[gt_seg.dtype], _p(gt_cls), _PRED_KINDS[gt_cls.dtype], _p(mask), B, H, W,
+                               n_class, ignore, max_segments, 0 if out is None else 1, _p(counts), _p(iou_sum), _p(matches),
+                               _p(status), _p(ws), ws.numel() * 8, _stream())
+    return counts, iou_sum, status, matches
+
+
 # -- set-level metrics: Laplacian pyramid, segmented sort, sliced Wasserstein distance (include/him.h "Set-level metrics")
 SWD_PATCH, SORT_LDS_MAX, SWD_ZERO_DEVIATION = 7, 8192, 1
 _SWD_WS = {}            # (tag, shape..., device index) -> cached workspace; one stream at a time per shape

@@ -1,8 +1,9 @@
 """Evaluation metrics on the device: SSIM / PSNR / L1 of a generated image against the real one (inside the edited box),
 pixel accuracy and IoU of a predicted layout, IoU of a generated object mask, and the contour measures of both (boundary
-F-score, average symmetric surface distance, Hausdorff distance, the "trimap" band) on an exact distance transform.  The
-reference ships no metric code; the definitions are those of include/him.h "Evaluation metrics" and "Distance transform
-and boundary metrics".  Every function queues device work on the current stream
+F-score, average symmetric surface distance, Hausdorff distance, the "trimap" band) on an exact distance transform, and
+the panoptic quality of a layout (instances matched at IoU > 0.5).  The
+reference ships no metric code; the definitions are those of include/him.h "Evaluation metrics", "Distance transform
+and boundary metrics" and "Panoptic matching".  Every function queues device work on the current stream
 and returns device tensors; nothing synchronises with the host before ``Evaluator.summary()`` as long as every argument
 is a device tensor: a ``box`` given as a list or array (and any host tensor) is copied to the device first, which waits
 on the host.  The device calls share one cached workspace per shape and device (``ops.image_metrics`` /
@@ -247,6 +248,70 @@ def boundary_band(gt, radius):
     g = _id_planes(gt, ())
     dist2 = ops.distance_transform(g, rule='any_boundary')[0]
     return (dist2 <= int(math.floor(float(radius) ** 2))).float().unsqueeze(1)
+
+
+def panoptic_scores(counts, iou_sum, things=None):
+    """Panoptic quality from the (n, 3) tp / fp / fn counts and the (n,) IoU sums of ``ops.panoptic_match``, in float64
+    on the host.  Per class ``pq = iou / (tp + fp/2 + fn/2)``, ``sq = iou / tp``, ``rq = tp / (tp + fp/2 + fn/2)``, each
+    nan where its denominator is 0.  ``pq`` and ``rq`` are the means over the classes with tp + fp + fn > 0, ``sq`` the
+    mean over those of them where it is defined (tp > 0); classes seen in neither map are counted in ``n_absent``.  With
+    ``things`` (the class ids that have instances) also ``pq_things`` and ``pq_stuff``, the same mean over the two groups."""
+    c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    s = iou_sum.detach().cpu().numpy() if torch.is_tensor(iou_sum) else np.asarray(iou_sum)
+    c, s = c.reshape(-1, 3).astype(np.float64), s.reshape(-1).astype(np.float64)
+    tp, den = c[:, 0], c[:, 0] + 0.5 * c[:, 1] + 0.5 * c[:, 2]
+    seen = c.sum(1) > 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        pq = np.where(den > 0, s / den, np.nan)
+        sq = np.where(tp > 0, s / tp, np.nan)
+        rq = np.where(den > 0, tp / den, np.nan)
+    out = OrderedDict([('pq', _nanmean(pq[seen])), ('sq', _nanmean(sq[seen])), ('rq', _nanmean(rq[seen]))])
+    if things is not None:
+        is_thing = np.zeros(len(pq), bool)
+        is_thing[[int(t) for t in things if 0 <= int(t) < len(pq)]] = True
+        out['pq_things'], out['pq_stuff'] = _nanmean(pq[seen & is_thing]), _nanmean(pq[seen & ~is_thing])
+    out['per_class_pq'], out['n_absent'] = pq, int((~seen).sum())
+    return out
+
+
+def _seg_planes(t):
+    t = _plane(t)
+    if t.dtype not in (torch.uint8, torch.int32, torch.int64):
+        t = t.to(torch.int32)
+    return t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous()
+
+
+def panoptic_quality(pred, gt, n_class, things, gt_inst=None, connectivity=8, min_area=1, ignore_label=None, mask=None,
+                     out=None, max_segments=1024):
+    """``(counts, iou_sum, status)`` of ``ops.panoptic_match`` on the device for a predicted layout against the ground
+    truth.  ``pred``, ``gt``: what ``confusion_matrix`` accepts (scores and probabilities go through ``ops.label_ids``).
+    Predicted segments are the connected components of the classes in ``things`` (``ops.label_instances_launch``; every
+    other class is one segment per plane); ground-truth segments come from ``gt_inst`` (the dataset's instance map, ids
+    0..65535) when given, else from the same labelling of ``gt``.  A labelling that reports a flag of its own (more than
+    ``max_segments`` objects, a class outside 0..255) sets ``ops.PQ_CCL`` in that plane's status on the device.  ``out``
+    accumulates.  No host synchronisation."""
+    p = _id_planes(pred, ('comb_pred_label', 'comb_recon_label'))
+    g = _id_planes(gt, ()).to(p.device)
+    if p.shape != g.shape:
+        raise ValueError('panoptic_quality: pred %s and gt %s differ' % (tuple(p.shape), tuple(g.shape)))
+    label = dict(connectivity=connectivity, min_area=min_area, max_objects=int(max_segments))
+    p_seg, _, st = ops.label_instances_launch(p, things, **label)
+    ccl = st['out'][:, 1].clone()            # the next labelling of this shape overwrites the record
+    if gt_inst is None:
+        g_seg, _, st = ops.label_instances_launch(g, things, **label)
+        ccl = ccl | st['out'][:, 1]
+    else:
+        g_seg = _seg_planes(gt_inst).to(p.device)
+    if mask is not None:
+        mask = mask.to(p.device).float()
+    res = ops.panoptic_match(p_seg, p, g_seg, g, n_class, mask=mask, ignore=-1 if ignore_label is None else int(ignore_label),
+                             max_segments=max_segments, out=out)
+    res[2][:, 2].bitwise_or_((ccl != 0).to(torch.int32) * ops.PQ_CCL)
+    return res[:3]
+
+
+PANOPTIC_KEYS = ('pq', 'sq', 'rq', 'pq_things', 'pq_stuff', 'per_class_pq', 'n_segments_gt', 'n_segments_pred',
+                 'panoptic_flags')
 
 
 def swd_tables(seed, C, n_dirs=512, device='cuda'):
@@ -584,7 +649,7 @@ class Evaluator(object):
     last entry is the generated tensor).  Nothing crosses to the host before ``summary()``."""
 
     def __init__(self, label_nc, data_range=255., as_bytes=True, boundary_tolerance=None, band_radius=None, swd=None,
-                 features=None):
+                 features=None, panoptic=None):
         self.label_nc, self.data_range, self.as_bytes = int(label_nc), float(data_range), bool(as_bytes)
         self._image, self._conf, self._mask, self._layouts = [], None, [], 0
         # opt-in contour measures: the tolerance of the boundary F-score in pixels, the radius of the trimap band
@@ -597,6 +662,17 @@ class Evaluator(object):
         # adds PRDC_KEYS to the summary)
         self._features = None if features is None or features is False else \
             FeatureDistance(**({} if features is True else dict(features)))
+        # opt-in panoptic quality: True, or a dict of things, connectivity, min_area, ignore_label, max_segments
+        self._pq_opt, self._pq, self._pq_tot = None, None, None
+        if panoptic is not None and panoptic is not False:
+            opt = dict(things=ops.CITYSCAPES_THINGS, connectivity=8, min_area=1, ignore_label=None, max_segments=1024)
+            given = {} if panoptic is True else dict(panoptic)
+            unknown = sorted(set(given) - set(opt))
+            if unknown:
+                raise ValueError('Evaluator: panoptic options %s (known: %s)' % (unknown, sorted(opt)))
+            opt.update(given)
+            opt['things'] = tuple(int(c) for c in opt['things'])
+            self._pq_opt = opt
 
     def add_image(self, fake, real, box=None):
         fake = _labels(fake, ('fake_image',))
@@ -608,7 +684,7 @@ class Evaluator(object):
             self._features.add(fake, real)
         return self
 
-    def add_layout(self, pred, gt, mask=None):
+    def add_layout(self, pred, gt, mask=None, gt_inst=None):
         if self._conf is None:
             pred_t = _plane(_labels(pred, ('comb_pred_label', 'comb_recon_label')))
             with torch.cuda.device(pred_t.device):
@@ -630,7 +706,22 @@ class Evaluator(object):
                     self._band = (torch.zeros((1, self.label_nc, self.label_nc), dtype=torch.int64, device=band.device),
                                   torch.zeros(2, dtype=torch.int32, device=band.device))
             confusion_matrix(pred, gt, self.label_nc, mask=band, out=self._band)
+        if self._pq_opt is not None:
+            self._add_panoptic(pred, gt, mask, gt_inst)
         return self
+
+    def _add_panoptic(self, pred, gt, mask, gt_inst):
+        p = _id_planes(pred, ('comb_pred_label', 'comb_recon_label'))
+        dev, n = p.device, self.label_nc
+        with torch.cuda.device(dev):
+            if self._pq is None:
+                self._pq = (torch.zeros((n, 3), dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev))
+                self._pq_tot = torch.zeros(3, dtype=torch.int64, device=dev)        # segments gt, pred, flag bits
+            status = torch.zeros((p.shape[0], 4), dtype=torch.int32, device=dev)   # per call: batches may differ in size
+        panoptic_quality(p, gt, n, gt_inst=gt_inst, mask=mask, out=self._pq + (status,), **self._pq_opt)
+        self._pq_tot[:2] += status[:, :2].sum(0)
+        bits = torch.arange(5, device=dev)
+        self._pq_tot[2] |= ((((status[:, 2:3].long() >> bits) & 1).amax(0)) << bits).sum()
 
     def add_object_mask(self, prob, gt):
         self._mask.append(mask_iou(prob, gt))
@@ -685,6 +776,15 @@ class Evaluator(object):
             if self._features.nearest_k is not None:
                 out.update((key, float(v.item())) for key, v in self._features.prdc().items())
                 out['nearest_k'] = int(self._features.nearest_k)
+        if self._pq_opt is not None:
+            out.update((k, nan) for k in PANOPTIC_KEYS)
+            out.update(per_class_pq=[], n_segments_gt=0, n_segments_pred=0, panoptic_flags=0)
+            if self._pq is not None:
+                sc = panoptic_scores(self._pq[0], self._pq[1], self._pq_opt['things'])
+                tot = self._pq_tot.cpu().numpy()
+                out.update((k, sc[k]) for k in ('pq', 'sq', 'rq', 'pq_things', 'pq_stuff'))
+                out.update(per_class_pq=[None if math.isnan(v) else float(v) for v in sc['per_class_pq']],
+                           n_segments_gt=int(tot[0]), n_segments_pred=int(tot[1]), panoptic_flags=int(tot[2]))
         return out
 
     def write_json(self, path):
