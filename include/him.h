@@ -938,6 +938,46 @@ int him_boundary_stats(const void* src, int kind, int B, int H, int W, const int
 int him_label_ids(const float* src, int pred_kind, int B, int C, int H, int W, int* ids, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Feathered canvas composite (the reference ships none: its paste_canvas replaces the whole output window as a hard
+ * rectangle).  The image paste of a joint edit with a matte: full strength on and near the pixels the layout edit
+ * changed, fading with the exact Euclidean distance to them, and fading towards every side of the paste window that has
+ * photograph behind it.  Everything on `stream`, no host synchronisation, no workspace, no atomics, results bit-identical
+ * from run to run.
+ *
+ * him_canvas_changed: changed[y][x] = before[y0+y][x0+x] != after[y0+y][x0+x], stored as 0 / 1; before / after are
+ *   one-channel fp32 id canvases (Hc,Wc), never written; changed is an (H,W) uint8 plane: what him_edt reads as kind 0
+ *   under HIM_EDT_NONZERO.  HIM_E_INVALID before any launch for a NULL pointer, H or W < 1 or a window
+ *   [y0,y0+H) x [x0,x0+W) not inside the canvas.
+ *
+ * him_canvas_paste_blend_v: him_canvas_paste_bicubic_v's column pass (same tmp (rows,W,3), tables and byte arithmetic)
+ *   with a matte.  P = byte / 255 (what that call would write), O = the canvas value already there.  For window pixel
+ *   (x, y) every decision is an integer comparison:
+ *     border term  d_b = min over the window sides NOT on the canvas edge of: left (x0 > 0) x + 1; right (x0 + W < Wc)
+ *                  W - x; top (y0 > 0) y + 1; bottom (y0 + H < Hc) H - y.  No side counts: t_b = 1.  Otherwise
+ *                  t_b = 1 if d_b >= feather, else (float)d_b / (float)feather.
+ *     object term  dist2 NULL: t_o = 1.  Otherwise d2 = dist2[y][x] (int32 (H,W), a him_edt result over `changed`):
+ *                  d2 == HIM_EDT_NONE: 0;  d2 <= reach^2: 1;  d2 >= (reach + feather)^2: 0 (64-bit comparisons);
+ *                  otherwise t_o = 1 - (sqrtf((float)d2) - reach) / feather.
+ *     matte        t = min(t_b, t_o); alpha = t (HIM_MATTE_LINEAR) or t * t * (3 - 2 t) (HIM_MATTE_SMOOTH); t = 0 and
+ *                  t = 1 give exactly 0 and 1.  fp32, every operation rounded on its own (no contraction).
+ *     canvas       alpha == 1: canvas = P, bit for bit;  alpha == 0: untouched (not even read);  otherwise
+ *                  canvas = O + alpha * (P - O) in fp32.  One alpha for the three channels of canvas (3,Hc,Wc).
+ *   matte: NULL, or fp32 (H,W) receiving alpha.  Nothing outside the window is read or written; each canvas element is
+ *   read and written by one thread.  HIM_E_INVALID before any launch, outputs untouched, for a NULL tmp / first / count /
+ *   weights / canvas, H, W or ksize < 1, a window not inside the canvas, feather outside 1..16384, reach outside
+ *   0..16384, an unknown profile.
+ *   Kernel layout: a 256-thread workgroup per tile of 64 columns x 4 rows of the window, lane = column, a wave per row,
+ *   a pixel per thread; canvas, dist2 and matte rows move as 256 contiguous bytes per wave.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_MATTE_LINEAR 0
+#define HIM_MATTE_SMOOTH 1
+int him_canvas_changed(const float* before, const float* after, int Hc, int Wc, int x0, int y0, int H, int W,
+                       unsigned char* changed, void* stream);
+int him_canvas_paste_blend_v(const unsigned char* tmp, const int* first, const int* count, const int* weights, int ksize,
+                             float* canvas, int Hc, int Wc, int x0, int y0, int H, int W, const int* dist2, int feather,
+                             int reach, int profile, float* matte, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Set-level metrics (the reference ships none): the sliced Wasserstein distance between the Laplacian-pyramid patches of
  * two SETS of images (Karras et al., "Progressive Growing of GANs", ICLR 2018, section 5 and its sliced_wasserstein.py).
  * No network, no weights; everything on `stream`, no host synchronisation, no allocation, results bit-identical from

@@ -156,6 +156,9 @@ _SIGS = {
     'him_boundary_stats_workspace': (c_size_t, [c_int, c_int, c_int]),
     'him_boundary_stats': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, c_size_t, P]),
     'him_label_ids': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'him_canvas_changed': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'him_canvas_paste_blend_v': (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int,
+                                         c_int, P, P]),
     'him_lap_levels': (C.c_uint, [c_int, c_int, c_int]),
     'him_lap_level_offset': (C.c_longlong, [c_int] * 5),
     'him_lap_pyramid_ws': (c_size_t, [c_int] * 5),

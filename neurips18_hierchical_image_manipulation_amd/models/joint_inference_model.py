@@ -10,7 +10,7 @@ import torch
 
 from ..data.base_dataset import NEAREST, get_raw_transform_fn
 from ..data.device import ImageTransform
-from ..util.data_util import _paste_image, crop_canvas, paste_canvas
+from ..util.data_util import _blend_args, _paste_image, crop_canvas, paste_canvas
 from ..util.util import load_script_to_opt
 
 
@@ -59,6 +59,19 @@ class JointInference(object):
 
     def gen_image(self, bbox_sampled, img_original, label_generated, opt):
         """-> (photo canvas with the generated pixels pasted in, crop_canvas's dict, the generator's (1,3,fs,fs) output)."""
+        return self.gen_image_feathered(bbox_sampled, img_original, label_generated, opt)
+
+    def gen_image_feathered(self, bbox_sampled, img_original, label_generated, opt, *, feather=None, reach=0,
+                            profile='smooth', label_before=None):
+        """``gen_image`` (which keeps the reference's exact parameter list) with the blended paste's options
+        (util/data_util.py ``_paste_image``).  ``feather=None`` IS ``gen_image``.  With ``feather`` the
+        generated pixels enter the photo canvas through a matte, left in ``input_dict['matte']`` (1,1,H,W) (a picture
+        through ``tensor2im(matte[0], normalize=False)``); with ``label_before``, the label canvas ``gen_layout`` was given
+        (``label_generated`` being the one it returned), only pixels within ``reach + feather`` of what the layout edit
+        changed are touched."""
+        # refuse bad options before crop_canvas draws its random numbers
+        _blend_args(img_original, feather, reach, profile, label_before, None if label_before is None else label_generated,
+                    False)
         input_dict = crop_canvas(bbox_sampled, label_generated, opt, img_original=img_original, transform_img=True)
         with torch.no_grad():
             img_generated = self.G_mask2img.inference(input_dict['label'], torch.zeros_like(input_dict['label']),
@@ -66,6 +79,12 @@ class JointInference(object):
                                                       input_dict['mask_out'])
         # paste_canvas(img_original, (img_generated + 1) / 2, input_dict, method=BICUBIC, is_img=True) with the
         # (x + 1) / 2 folded into the paste's quantisation (same fp32 operations)
-        img_canvas = _paste_image(img_original, img_generated, input_dict, 2)
+        if feather is None:
+            img_canvas = _paste_image(img_original, img_generated, input_dict, 2)
+        else:
+            img_canvas, input_dict['matte'] = _paste_image(
+                img_original, img_generated, input_dict, 2, feather=feather, reach=reach, profile=profile,
+                label_before=label_before, label_after=None if label_before is None else label_generated,
+                want_matte=True)
         return img_canvas, input_dict, img_generated
 

@@ -2271,7 +2271,7 @@ def canvas_paste_bicubic(patch, box, canvas, x0, y0, H, W, pre=0):
     return _bicubic(patch, box, H, W, pre, canvas, (x0, y0), False)
 
 
-def _bicubic(src, box, H, W, pre, canvas, at, normalize):
+def _bicubic(src, box, H, W, pre, canvas, at, normalize, blend=None):
     import numpy as np
     from .data import resample
     C, Hs, Ws = _plane_geometry(src, 'canvas bicubic')
@@ -2295,8 +2295,65 @@ def _bicubic(src, box, H, W, pre, canvas, at, normalize):
         lib.him_data_bicubic_v(_p(tmp), h, afy, any_, awy, ksy, fl, _p(dst), 1 if normalize else 0, 1, H, W, st)
         return dst
     _, Hc, Wc = _plane_geometry(canvas, 'canvas_paste_bicubic')
-    lib.him_canvas_paste_bicubic_v(_p(tmp), afy, any_, awy, ksy, _p(canvas), Hc, Wc, int(at[0]), int(at[1]), H, W, st)
+    if blend is None:
+        lib.him_canvas_paste_bicubic_v(_p(tmp), afy, any_, awy, ksy, _p(canvas), Hc, Wc, int(at[0]), int(at[1]), H, W, st)
+        return canvas
+    dist2, feather, reach, profile, matte = blend
+    lib.him_canvas_paste_blend_v(_p(tmp), afy, any_, awy, ksy, _p(canvas), Hc, Wc, int(at[0]), int(at[1]), H, W,
+                                 _p(dist2), feather, reach, profile, _p(matte), st)
     return canvas
+
+
+MATTE_PROFILES = {'linear': 0, 'smooth': 1}
+MATTE_MAX_RADIUS = 16384
+
+
+def matte_args(feather, reach, profile, what):
+    """(feather, reach, profile number) of a blended paste, checked on the host: ``feather`` 1..16384 pixels of ramp,
+    ``reach`` 0..16384 pixels of full strength around the changed pixels, ``profile`` in ``MATTE_PROFILES``."""
+    for name, v, lo in (('feather', feather, 1), ('reach', reach, 0)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= MATTE_MAX_RADIUS:
+            raise ValueError('%s: %s must be an int in %d..%d, got %r' % (what, name, lo, MATTE_MAX_RADIUS, v))
+    if profile not in MATTE_PROFILES:
+        raise ValueError('%s: profile %r (one of %s)' % (what, profile, ', '.join(MATTE_PROFILES)))
+    return feather, reach, MATTE_PROFILES[profile]
+
+
+def canvas_changed(before, after, x0, y0, H, W):
+    """(1,H,W) uint8 on the device: 1 where the one-channel fp32 id canvases ``before`` and ``after`` (1,1,Hc,Wc) differ
+    inside the window [y0,y0+H) x [x0,x0+W), which must lie inside them -- the seed plane ``distance_transform`` reads
+    under ``rule='nonzero'``.  Current stream, no host synchronisation."""
+    C, Hc, Wc = _plane_geometry(before, 'canvas_changed')
+    if C != 1 or tuple(after.shape) != tuple(before.shape) or after.device != before.device:
+        raise HimError('canvas_changed: two (1,1,Hc,Wc) label canvases of one shape on one device, got %s and %s'
+                       % (tuple(before.shape), tuple(after.shape)))
+    _chk(after)
+    x0, y0, H, W = int(x0), int(y0), int(H), int(W)
+    if H < 1 or W < 1 or x0 < 0 or y0 < 0 or x0 + W > Wc or y0 + H > Hc:
+        raise HimError('canvas_changed: window (%d,%d)+(%d,%d) outside the %dx%d canvas' % (x0, y0, W, H, Wc, Hc))
+    changed = torch.empty((1, H, W), dtype=torch.uint8, device=before.device)
+    lib.him_canvas_changed(_p(before), _p(after), Hc, Wc, x0, y0, H, W, _p(changed), _stream())
+    return changed
+
+
+def canvas_paste_blend(patch, box, canvas, x0, y0, H, W, pre=0, feather=8, reach=0, dist2=None, profile='smooth',
+                       want_matte=False):
+    """``canvas_paste_bicubic`` through a matte, in place -> ``(canvas, matte or None)``.  The matte fades over ``feather``
+    pixels towards every side of the window that is not on the canvas edge and, with ``dist2`` (int32 (H,W) or (1,H,W):
+    ``distance_transform``'s squared distances to the pixels an edit changed), from full strength within ``reach`` pixels
+    of them to nothing at ``reach + feather``; ``profile`` 'linear' or 'smooth' (smoothstep).  Where the matte is 1 the
+    canvas receives exactly what ``canvas_paste_bicubic`` writes, where it is 0 it keeps its pixel (include/him.h
+    "Feathered canvas composite").  ``matte``: (1,1,H,W) fp32.  Current stream, no host synchronisation."""
+    feather, reach, profile = matte_args(feather, reach, profile, 'canvas_paste_blend')
+    H, W = int(H), int(W)
+    if dist2 is not None:
+        if not torch.is_tensor(dist2) or not dist2.is_cuda or dist2.dtype != torch.int32 or dist2.device != canvas.device \
+                or tuple(dist2.shape) not in ((H, W), (1, H, W)):
+            raise HimError('canvas_paste_blend: dist2 must be an int32 (%d,%d) tensor on the canvas device' % (H, W))
+        dist2 = dist2.contiguous()
+    matte = torch.empty((1, 1, H, W), dtype=torch.float32, device=canvas.device) if want_matte else None
+    _bicubic(patch, box, H, W, pre, canvas, (x0, y0), False, (dist2, feather, reach, profile, matte))
+    return canvas, matte
 
 
 def canvas_paste_window(src, canvas, x0, y0):

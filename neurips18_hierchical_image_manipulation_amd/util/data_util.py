@@ -91,9 +91,35 @@ def _slice_len(start, stop, size):
     return max(0, min(stop, size) - min(start, size))
 
 
-def _paste_image(original, cropped, info_dict, pre):
+def _blend_args(original, feather, reach, profile, label_before, label_after, want_matte):
+    """The blended paste's options, checked on the host before any device work -> None (``feather`` None: the hard
+    paste) or (feather, reach, profile)."""
+    if feather is None:
+        if label_before is not None or label_after is not None or want_matte or reach != 0:
+            raise ValueError('paste_canvas: reach / label_before / label_after / want_matte need feather')
+        return None
+    ops.matte_args(feather, reach, profile, 'paste_canvas')
+    if (label_before is None) != (label_after is None):
+        raise ValueError('paste_canvas: label_before and label_after come together')
+    for name, lab in (('label_before', label_before), ('label_after', label_after)):
+        if lab is not None and (lab.dim() != 4 or tuple(lab.shape[:2]) != (1, 1) or
+                                tuple(lab.shape[2:]) != tuple(original.shape[2:])):
+            raise ValueError('paste_canvas: %s %s is not a (1,1,%d,%d) label canvas of the photo canvas'
+                             % (name, tuple(lab.shape), original.shape[2], original.shape[3]))
+    return feather, reach, profile
+
+
+def _paste_image(original, cropped, info_dict, pre, *, feather=None, reach=0, profile='smooth', label_before=None,
+                 label_after=None, want_matte=False):
     """The is_img branch: the ``output_bbox`` slice of ``cropped`` (1,3,fs,fs), ToPILImage of pre(v), BICUBIC to the
-    global window, ToTensor, written into a clone of ``original``."""
+    global window, ToTensor, written into a clone of ``original``.
+
+    ``feather`` (pixels, None: the hard rectangle above, unchanged) writes through a matte instead: it
+    fades over ``feather`` pixels towards every side of the window with photograph behind it and, given the label canvas
+    before and after the layout edit, from full strength within ``reach`` pixels of the pixels the edit changed to nothing
+    at ``reach + feather`` (``canvas_changed`` -> ``distance_transform`` -> the blended paste); ``profile`` 'linear' or
+    'smooth'.  ``want_matte``: -> (canvas, matte (1,1,H,W))."""
+    blend = _blend_args(original, feather, reach, profile, label_before, label_after, want_matte)
     x1, y1, x2, y2 = _window(info_dict['output_bbox_global'])
     width, height = x2 - x1 + 1, y2 - y1 + 1
     x3, y3, x4, y4 = (int(v) for v in info_dict['output_bbox'].int())
@@ -106,8 +132,32 @@ def _paste_image(original, cropped, info_dict, pre):
         raise ValueError('paste_canvas: a %dx%d patch window does not fit the %dx%d canvas window at (%d,%d)'
                          % (sw, sh, width, height, x1, y1))
     raw = original.clone()
-    ops.canvas_paste_bicubic(cropped.contiguous(), (x3, y3, x3 + sw, y3 + sh), raw, x1, y1, height, width, pre)
-    return raw
+    if blend is None:
+        ops.canvas_paste_bicubic(cropped.contiguous(), (x3, y3, x3 + sw, y3 + sh), raw, x1, y1, height, width, pre)
+        return raw
+    dist2 = None
+    if label_before is not None:
+        changed = ops.canvas_changed(label_before.contiguous(), label_after.contiguous(), x1, y1, height, width)
+        dist2 = ops.distance_transform(changed, rule='nonzero')[0]
+    _, matte = ops.canvas_paste_blend(cropped.contiguous(), (x3, y3, x3 + sw, y3 + sh), raw, x1, y1, height, width, pre,
+                                      feather=feather, reach=reach, dist2=dist2, profile=profile, want_matte=want_matte)
+    return (raw, matte) if want_matte else raw
+
+
+def paste_canvas_feathered(original, cropped, info_dict, method=BICUBIC, resize=True, is_img=True, *, feather=None,
+                           reach=0, profile='smooth', label_before=None, label_after=None, want_matte=False):
+    """``paste_canvas`` with the blended image paste's options (see ``_paste_image``).  ``paste_canvas`` itself keeps the
+    reference's exact parameter list, so the options live here; ``feather=None`` IS ``paste_canvas``.  A label paste
+    (``is_img`` False) has nothing to blend: with ``feather`` it raises ValueError."""
+    if feather is not None and not is_img:
+        raise ValueError('paste_canvas: feather blends an image paste; a label map (is_img=False) is copied')
+    blend = _blend_args(original, feather, reach, profile, label_before, label_after, want_matte)
+    if blend is None:
+        return paste_canvas(original, cropped, info_dict, method=method, resize=resize, is_img=is_img)
+    if method != BICUBIC:
+        raise NotImplementedError('paste_canvas(is_img=True): only Image.BICUBIC is on the HIP path')
+    return _paste_image(original, cropped, info_dict, 0, feather=feather, reach=reach, profile=profile,
+                        label_before=label_before, label_after=label_after, want_matte=want_matte)
 
 
 def paste_canvas(original, cropped, info_dict, method=NEAREST, resize=True, is_img=False):
