@@ -413,6 +413,17 @@ int him_conv2d_in_act_fwd(const HimConv2d* d, const float* x, const float* w, co
                           float* y_raw, const float* residual, float* z, float* mean, float* rstd, float eps, int act,
                           float slope, void* ws, size_t ws_bytes, void* stream);
 
+/* Return codes of the elementwise, encoding, pooling and spectral-norm entries below (him_act_bwd ... him_maxpool_relu_bwd,
+ * him_fill, him_scale, him_sn_*, him_div_scalar_*), all decided on the host before any launch; a refused call writes nothing:
+ *   flat entries taking `size_t n` (him_act_bwd, him_add, him_fill, him_scale, him_u8_to_f32, him_div_scalar_*): n == 0 is
+ *     HIM_OK and launches nothing, whatever the pointers; a null pointer with n > 0 is HIM_E_INVALID.
+ *   shaped entries: HIM_E_INVALID for a non-positive B / planes / C / label_nc / hw / H / W / rows / cols, for a channel
+ *     slice outside [0, Ctot) (c0 < 0 or c0 + n > Ctot; likewise cs0 / cd0 / ca0 / cb0), for OH / OW other than
+ *     (H - 1) / 2 + 1, (W - 1) / 2 + 1, for k <= 0 or k larger than H or W, and for a null pointer other than the ones named
+ *     optional below (him_masked_image's three outputs, him_masked_mean's noise, him_copy_channels' mask at mask_mode 0,
+ *     him_sn_power_iter_bwd's u_out and sigma, which it does not read).  him_copy_channels: n < 0 is HIM_E_INVALID, n == 0
+ *     with a valid slice is HIM_OK without a launch.
+ *   HIM_E_WORKSPACE: ws null or ws_bytes below the size the entry names. */
 /* dz = dy * act'(.) expressed through the activation OUTPUT y (ReLU/LeakyReLU/Tanh epilogues). */
 int him_act_bwd(const float* y, const float* dy, float* dz, size_t n, int act, float slope, void* stream);
 /* out = a + b  (gradient fan-in, residual adds) */
@@ -451,7 +462,9 @@ int him_tile_embed(const float* emb, const float* mask, float* dst, int B, int C
 int him_copy_channels(const float* src, int Csrc, int cs0, float* dst, int Cdst, int cd0, int n, int B,
                       int hw, const float* mask, int mask_mode, int accumulate, void* stream);
 /* out = (1-m)*a + m*b with a, b channel slices: output gate models/Pix2Pix_NET.py:96-99,242-245 and the
- * two-stream fusion :215-217.  m is (B,1,HW). */
+ * two-stream fusion :215-217.  m is (B,1,HW).  The sum is contracted (one fused multiply-add): with a 0/1 mask the result
+ * is a or b exactly; with a fractional mask it is within one rounding of the exact value, not torch's two roundings.  The
+ * same holds for him_copy_channels with accumulate and a mask. */
 int him_blend(const float* a, int Ca, int ca0, const float* b, int Cb, int cb0, const float* m, float* out,
               int B, int C, int hw, void* stream);
 
@@ -459,7 +472,8 @@ int him_blend(const float* a, int Ca, int ca0, const float* b, int Cb, int cb0, 
 int him_avgpool3s2_fwd(const float* x, float* y, int planes, int H, int W, int OH, int OW, void* stream);
 int him_avgpool3s2_bwd(const float* dy, float* dx, int planes, int H, int W, int OH, int OW, void* stream);
 /* nn.MaxPool2d(k, k): VGG19 2x2 pools (models/layer_util.py:383) and the 2^n mask pool
- * (models/Pix2Pix_NET.py:134). bwd routes to the first maximum in row-major window order. */
+ * (models/Pix2Pix_NET.py:134). bwd routes to the first maximum in row-major window order and writes every element of dx:
+ * rows and columns that no window covers (H or W not a multiple of k) get 0. */
 int him_maxpool_fwd(const float* x, float* y, int planes, int H, int W, int k, void* stream);
 int him_maxpool_bwd(const float* x, const float* dy, float* dx, int planes, int H, int W, int k, void* stream);
 /* the same for a pool that follows a ReLU whose backward is folded in: windows with a non-positive maximum pass nothing */
@@ -470,6 +484,10 @@ int him_maxpool_relu_bwd(const float* x, const float* dy, float* dx, int planes,
  * pix2pixHD_condImg_model.py:235-251 and models/losses.py:75-82.  Deterministic two-stage reductions.
  *   *_fwd : out[0] = mean(...)     (device scalar)
  *   *_bwd : d(in) (+)= g[0] * d mean / d in     (g = device scalar upstream gradient)
+ *   HIM_E_INVALID: n == 0 in a *_fwd (the mean of nothing), him_lincomb_* with n outside 1..8 or a null table;
+ *   HIM_E_WORKSPACE: ws null or ws_bytes < him_reduce_ws(n) / him_l1_multi_ws(npairs).  *_bwd with n == 0, and
+ *   him_l1_multi_* with npairs <= 0, are HIM_OK and launch nothing.  All of these return before any launch, except an
+ *   empty pair (n[i] == 0) inside him_l1_multi_fwd, which is found after the preceding table of 16 pairs was launched.
  * ------------------------------------------------------------------------------------------- */
 size_t him_reduce_ws(size_t n);
 int him_l1_mean_fwd(const float* a, const float* b, size_t n, float* out, void* ws, size_t ws_bytes,
@@ -573,6 +591,7 @@ int him_adam_guarded_step(float* p, const float* g, float* m, float* v, float* e
  *   differentiates through both normalisations.
  *   fwd: v_out[cols], u_out[rows], sigma_out[1]; scratch t[rows], s[cols] live in ws.
  *   bwd: dW (+)= g_sigma * d sigma / dW   given the saved u (input), v_out, u_out.
+ *   ws: him_sn_ws(rows, cols) bytes for either pass.  W == 0 gives v = u' = sigma = 0 and dW (+)= 0 exactly.
  * ------------------------------------------------------------------------------------------- */
 size_t him_sn_ws(int rows, int cols);
 int him_sn_power_iter_fwd(const float* W, const float* u, int rows, int cols, float* v_out, float* u_out,
@@ -580,7 +599,9 @@ int him_sn_power_iter_fwd(const float* W, const float* u, int rows, int cols, fl
 int him_sn_power_iter_bwd(const float* W, const float* u, const float* v_out, const float* u_out,
                           const float* sigma, const float* g_sigma, int rows, int cols, float* dW,
                           int accumulate, void* ws, size_t ws_bytes, void* stream);
-/* out = W / sigma[0] ; and the W-side of its backward: dW (+)= dWbar/sigma, dsigma = -sum(dWbar*W)/sigma^2 */
+/* out = W / sigma[0] ; and the W-side of its backward: dW (+)= dWbar/sigma, dsigma = -sum(dWbar*W)/sigma^2.
+ * him_div_scalar_bwd's ws holds one partial sum per block: min(ceil(n / 1024), 1024) floats; him_reduce_ws(n) bytes
+ * (what ops.py passes) are always enough.  HIM_E_WORKSPACE below that, or with ws null. */
 int him_div_scalar_fwd(const float* W, const float* sigma, float* out, size_t n, void* stream);
 int him_div_scalar_bwd(const float* W, const float* sigma, const float* dout, float* dW, float* dsigma,
                        size_t n, int accumulate, void* ws, size_t ws_bytes, void* stream);

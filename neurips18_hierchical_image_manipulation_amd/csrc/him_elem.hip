@@ -305,105 +305,136 @@ using namespace him;
 
 extern "C" {
 
+// Argument checks of this file's entry points: HIM_E_INVALID before any launch for a non-positive extent or a null pointer
+// with work to do (include/him.h states them per entry); n == 0 of the flat entries stays HIM_OK without a launch.
 int him_act_bwd(const float* y, const float* dy, float* dz, size_t n, int act, float slope, void* stream) {
   if (!n) return HIM_OK;
+  if (!y || !dy || !dz) return fail(HIM_E_INVALID, "act_bwd: null pointer");
   hipLaunchKernelGGL(act_bwd_kernel, gs_grid(n), dim3(256), 0, ST, y, dy, dz, n, act, slope);
   return check_launch("act_bwd");
 }
 int him_add(const float* a, const float* b, float* out, size_t n, void* stream) {
   if (!n) return HIM_OK;
+  if (!a || !b || !out) return fail(HIM_E_INVALID, "add: null pointer");
   hipLaunchKernelGGL(add_kernel, gs_grid(n), dim3(256), 0, ST, a, b, out, n);
   return check_launch("add");
 }
 int him_fill(float* p, size_t n, float value, void* stream) {
   if (!n) return HIM_OK;
+  if (!p) return fail(HIM_E_INVALID, "fill: null pointer");
   hipLaunchKernelGGL(fill_kernel, gs_grid(n), dim3(256), 0, ST, p, n, value);
   return check_launch("fill");
 }
 int him_scale(float* p, size_t n, float s, void* stream) {
   if (!n) return HIM_OK;
+  if (!p) return fail(HIM_E_INVALID, "scale: null pointer");
   hipLaunchKernelGGL(scale_kernel, gs_grid(n), dim3(256), 0, ST, p, n, s);
   return check_launch("scale");
 }
 int him_u8_to_f32(const unsigned char* src, float* dst, size_t n, void* stream) {
   if (!n) return HIM_OK;
+  if (!src || !dst) return fail(HIM_E_INVALID, "u8_to_f32: null pointer");
   hipLaunchKernelGGL(u8_to_f32_kernel, gs_grid(n), dim3(256), 0, ST, src, dst, n);
   return check_launch("u8_to_f32");
 }
 int him_masked_image(const float* image, const float* bbox, float* mask, float* masked_object, float* masked_context,
                      int B, int C, int H, int W, float cls2fill, void* stream) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "masked_image: bad shape");
+  if (!image || !bbox) return fail(HIM_E_INVALID, "masked_image: null pointer");
   hipLaunchKernelGGL(masked_image_kernel, gs_grid((size_t)B * C * H * W), dim3(256), 0, ST, image, bbox, mask,
                      masked_object, masked_context, B, C, H, W, cls2fill);
   return check_launch("masked_image");
 }
 int him_onehot(const float* label, float* dst, int B, int label_nc, int Ctot, int c0, int hw, void* stream) {
+  if (B <= 0 || label_nc <= 0 || hw <= 0) return fail(HIM_E_INVALID, "onehot: bad shape");
   if (c0 < 0 || c0 + label_nc > Ctot) return fail(HIM_E_INVALID, "onehot: channel slice out of range");
+  if (!label || !dst) return fail(HIM_E_INVALID, "onehot: null pointer");
   hipLaunchKernelGGL(onehot_kernel, gs_grid((long long)B * label_nc * hw), dim3(256), 0, ST, label, dst, B,
                      label_nc, Ctot, c0, hw);
   return check_launch("onehot");
 }
 int him_onehot_pool3s2(const float* label, float* dst, int B, int label_nc, int Ctot, int c0, int H, int W, int OH, int OW,
                        void* stream) {
+  if (B <= 0 || label_nc <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "onehot_pool: bad shape");
   if (c0 < 0 || c0 + label_nc > Ctot) return fail(HIM_E_INVALID, "onehot_pool: channel slice out of range");
   if (OH != (H + 2 - 3) / 2 + 1 || OW != (W + 2 - 3) / 2 + 1) return fail(HIM_E_INVALID, "onehot_pool: bad OH/OW");
+  if (!label || !dst) return fail(HIM_E_INVALID, "onehot_pool: null pointer");
   hipLaunchKernelGGL(onehot_pool3s2_kernel, gs_grid((long long)B * OH * OW), dim3(256), 0, ST, label, dst, B, label_nc,
                      Ctot, c0, H, W, OH, OW);
   return check_launch("onehot_pool3s2");
 }
 int him_edges(const float* inst, float* dst, int B, int H, int W, int Ctot, int c0, void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "edges: bad shape");
   if (c0 < 0 || c0 + 1 > Ctot) return fail(HIM_E_INVALID, "edges: channel slice out of range");
+  if (!inst || !dst) return fail(HIM_E_INVALID, "edges: null pointer");
   hipLaunchKernelGGL(edges_kernel, gs_grid((long long)B * H * W), dim3(256), 0, ST, inst, dst, B, H, W, Ctot, c0);
   return check_launch("edges");
 }
 int him_masked_mean(const float* image, const float* obj_mask, const float* noise, float* emb, int B, int hw,
                     void* stream) {
+  if (B <= 0 || hw <= 0) return fail(HIM_E_INVALID, "masked_mean: bad shape");
+  if (!image || !obj_mask || !emb) return fail(HIM_E_INVALID, "masked_mean: null pointer");
   hipLaunchKernelGGL(masked_mean_kernel, dim3(B * 3), dim3(256), 0, ST, image, obj_mask, noise, emb, hw);
   return check_launch("masked_mean");
 }
 int him_tile_embed(const float* emb, const float* mask, float* dst, int B, int Ctot, int c0, int hw, void* stream) {
+  if (B <= 0 || hw <= 0) return fail(HIM_E_INVALID, "tile_embed: bad shape");
   if (c0 < 0 || c0 + 3 > Ctot) return fail(HIM_E_INVALID, "tile_embed: channel slice out of range");
+  if (!emb || !mask || !dst) return fail(HIM_E_INVALID, "tile_embed: null pointer");
   hipLaunchKernelGGL(tile_embed_kernel, gs_grid((long long)B * 3 * hw), dim3(256), 0, ST, emb, mask, dst, B, Ctot,
                      c0, hw);
   return check_launch("tile_embed");
 }
 int him_copy_channels(const float* src, int Csrc, int cs0, float* dst, int Cdst, int cd0, int n, int B, int hw,
                       const float* mask, int mask_mode, int accumulate, void* stream) {
+  if (n < 0 || B <= 0 || hw <= 0) return fail(HIM_E_INVALID, "copy_channels: bad shape");
   if (cs0 < 0 || cs0 + n > Csrc || cd0 < 0 || cd0 + n > Cdst)
     return fail(HIM_E_INVALID, "copy_channels: slice out of range");
   if (mask_mode != 0 && !mask) return fail(HIM_E_INVALID, "copy_channels: mask_mode without mask");
+  if (!n) return HIM_OK;
+  if (!src || !dst) return fail(HIM_E_INVALID, "copy_channels: null pointer");
   hipLaunchKernelGGL(copy_channels_kernel, gs_grid((long long)B * n * hw), dim3(256), 0, ST, src, Csrc, cs0, dst,
                      Cdst, cd0, n, B, hw, mask, mask_mode, accumulate);
   return check_launch("copy_channels");
 }
 int him_blend(const float* a, int Ca, int ca0, const float* b, int Cb, int cb0, const float* m, float* out, int B,
               int C, int hw, void* stream) {
+  if (B <= 0 || C <= 0 || hw <= 0) return fail(HIM_E_INVALID, "blend: bad shape");
   if (ca0 < 0 || ca0 + C > Ca || cb0 < 0 || cb0 + C > Cb) return fail(HIM_E_INVALID, "blend: slice out of range");
+  if (!a || !b || !m || !out) return fail(HIM_E_INVALID, "blend: null pointer");
   hipLaunchKernelGGL(blend_kernel, gs_grid((long long)B * C * hw), dim3(256), 0, ST, a, Ca, ca0, b, Cb, cb0, m, out,
                      B, C, hw);
   return check_launch("blend");
 }
 int him_avgpool3s2_fwd(const float* x, float* y, int planes, int H, int W, int OH, int OW, void* stream) {
+  if (planes <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "avgpool: bad shape");
   if (OH != (H + 2 - 3) / 2 + 1 || OW != (W + 2 - 3) / 2 + 1) return fail(HIM_E_INVALID, "avgpool: bad OH/OW");
+  if (!x || !y) return fail(HIM_E_INVALID, "avgpool: null pointer");
   hipLaunchKernelGGL(avgpool3s2_fwd_kernel, gs_grid((long long)planes * OH * OW), dim3(256), 0, ST, x, y, planes, H,
                      W, OH, OW);
   return check_launch("avgpool_fwd");
 }
 int him_avgpool3s2_bwd(const float* dy, float* dx, int planes, int H, int W, int OH, int OW, void* stream) {
+  if (planes <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "avgpool: bad shape");
   if (OH != (H + 2 - 3) / 2 + 1 || OW != (W + 2 - 3) / 2 + 1) return fail(HIM_E_INVALID, "avgpool: bad OH/OW");
+  if (!dy || !dx) return fail(HIM_E_INVALID, "avgpool: null pointer");
   hipLaunchKernelGGL(avgpool3s2_bwd_kernel, gs_grid((long long)planes * H * W), dim3(256), 0, ST, dy, dx, planes, H,
                      W, OH, OW);
   return check_launch("avgpool_bwd");
 }
 int him_maxpool_fwd(const float* x, float* y, int planes, int H, int W, int k, void* stream) {
+  if (planes <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "maxpool: bad shape");
   if (k <= 0 || H / k <= 0 || W / k <= 0) return fail(HIM_E_INVALID, "maxpool: bad k");
+  if (!x || !y) return fail(HIM_E_INVALID, "maxpool: null pointer");
   hipLaunchKernelGGL(maxpool_fwd_kernel, gs_grid((long long)planes * (H / k) * (W / k)), dim3(256), 0, ST, x, y,
                      planes, H, W, k);
   return check_launch("maxpool_fwd");
 }
 static int maxpool_bwd_impl(const float* x, const float* dy, float* dx, int planes, int H, int W, int k, int relu_gate,
                             void* stream) {
+  if (planes <= 0 || H <= 0 || W <= 0) return fail(HIM_E_INVALID, "maxpool: bad shape");
   if (k <= 0 || H / k <= 0 || W / k <= 0) return fail(HIM_E_INVALID, "maxpool: bad k");
+  if (!x || !dy || !dx) return fail(HIM_E_INVALID, "maxpool: null pointer");
   if (H % k || W % k) {
     hipLaunchKernelGGL(zero_tail_kernel, gs_grid((long long)planes * H * W), dim3(256), 0, ST, dx, planes, H, W, k);
     int rc = check_launch("maxpool_tail");

@@ -490,6 +490,7 @@ size_t him_sn_ws(int rows, int cols) { return ((size_t)2 * rows + 3 * (size_t)co
 int him_sn_power_iter_fwd(const float* W, const float* u, int rows, int cols, float* v_out, float* u_out,
                           float* sigma_out, void* ws, size_t ws_bytes, void* stream) {
   if (rows <= 0 || cols <= 0) return fail(HIM_E_INVALID, "sn: bad shape");
+  if (!W || !u || !v_out || !u_out || !sigma_out) return fail(HIM_E_INVALID, "sn: null pointer");
   if (!ws || ws_bytes < him_sn_ws(rows, cols)) return fail(HIM_E_WORKSPACE, "sn: ws too small");
   float* t = (float*)ws;
   float* s = t + 2 * rows;
@@ -506,6 +507,7 @@ int him_sn_power_iter_bwd(const float* W, const float* u, const float* v_out, co
   (void)u_out;
   (void)sigma;
   if (rows <= 0 || cols <= 0) return fail(HIM_E_INVALID, "sn: bad shape");
+  if (!W || !u || !v_out || !g_sigma || !dW) return fail(HIM_E_INVALID, "sn: null pointer");
   if (!ws || ws_bytes < him_sn_ws(rows, cols)) return fail(HIM_E_WORKSPACE, "sn: ws too small");
   float* t = (float*)ws;
   float* a = t + rows;
@@ -525,6 +527,7 @@ int him_sn_power_iter_bwd(const float* W, const float* u, const float* v_out, co
 
 int him_div_scalar_fwd(const float* W, const float* sigma, float* out, size_t n, void* stream) {
   if (!n) return HIM_OK;
+  if (!W || !sigma || !out) return fail(HIM_E_INVALID, "div_scalar: null pointer");
   hipLaunchKernelGGL(div_scalar_fwd_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0,
                      ST, W, sigma, out, n);
   return check_launch("div_scalar_fwd");
@@ -533,7 +536,8 @@ int him_div_scalar_fwd(const float* W, const float* sigma, float* out, size_t n,
 int him_div_scalar_bwd(const float* W, const float* sigma, const float* dout, float* dW, float* dsigma, size_t n,
                        int accumulate, void* ws, size_t ws_bytes, void* stream) {
   if (!n) return HIM_OK;
-  const int nb = (int)std::min<size_t>((n + 1023) / 1024, 1024);
+  if (!W || !sigma || !dout || !dW || !dsigma) return fail(HIM_E_INVALID, "div_scalar: null pointer");
+  const int nb = (int)std::min<size_t>((n + 1023) / 1024, 1024);   // min(ceil(n / 1024), 1024) partial sums: include/him.h
   if (!ws || ws_bytes < (size_t)nb * sizeof(float)) return fail(HIM_E_WORKSPACE, "div_scalar: ws too small");
   hipLaunchKernelGGL(div_scalar_bwd1_kernel, dim3(nb), dim3(256), 0, ST, W, sigma, dout, dW, (float*)ws, n,
                      accumulate);

@@ -202,6 +202,93 @@ def dump_report(path):
     del REPORT[:]
 
 
+# ------------------------------------------------------------------------- guarded calls and per-tensor rows (shared)
+def bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def max_rel_err(got, ref):
+    """tests/README.md's metric as one number: maximum error over maximum |ref|; inf when an element is not finite."""
+    g, r = torch.as_tensor(got).detach().double().cpu().reshape(-1), torch.as_tensor(ref).detach().double().cpu().reshape(-1)
+    if r.numel() == 0:
+        return 0.0
+    err = (g - r).abs()
+    if not bool(torch.isfinite(err).all()):
+        return float('inf')
+    return float(err.max()) / max(float(r.abs().max()), 1e-30)
+
+
+def call(lib, dev, fn, specs, args, expect=0):
+    """One guarded call: ``args(P)`` builds the argument list from the arena's address function.  Checks the return
+    code, every band and that no input changed; returns the arena."""
+    ar = Arena(dev, specs)
+    rc = getattr(lib, fn)(*args(ar.ptr))
+    _sync(dev)
+    assert rc == expect, '%s returned %d, expected %d (%s)' % (fn, rc, expect, lib.him_last_error())
+    bad = ar.guard_failures()
+    assert not bad, '%s: %s' % (fn, '; '.join(bad))
+    for name, s in specs.items():
+        if s[0] == 'in':
+            assert torch.equal(bits(ar.t[name]), bits(s[1])), '%s wrote its input %s' % (fn, name)
+    return ar
+
+
+def untouched(ar, specs):
+    """After a refused call: fresh outputs and the workspace still hold the NaN bytes, prefilled outputs their prefill."""
+    for name, s in specs.items():
+        if s[0] == 'ws' or (s[0] == 'out' and s[2] is None):
+            assert bool((ar.t[name].view(torch.uint8) == NAN_BYTE).all()), name
+        elif s[0] == 'out':
+            assert torch.equal(bits(ar.t[name]), bits(s[2])), name
+
+
+class RowLog(object):
+    """The rows of one test module; ``flush()`` appends them to ``path`` as JSON lines."""
+
+    def __init__(self, path):
+        self.path, self.rows = path, []
+
+    def flush(self):
+        if self.rows:
+            os.makedirs(os.path.dirname(self.path), exist_ok=True)
+            with open(self.path, 'a') as f:
+                for r in self.rows:
+                    f.write(json.dumps(r) + '\n')
+            del self.rows[:]
+
+
+class Checks(object):
+    """Collects the rows of one case in ``log``; ``done()`` flushes, then asserts, after every row has been reported.
+    ``ref32`` of ``row`` may be a list of float32 results (several correct summation orders): e32 is their maximum."""
+
+    def __init__(self, case, log, flush=None, metric=max_rel_err, limit=DIRECT.limit):
+        self.case, self.failed, self.log = case, [], log
+        self.flush, self.metric, self.limit = flush or log.flush, metric, limit
+
+    def row(self, name, got, ref64, ref32, metric=None, lim=None):
+        metric = metric or self.metric
+        got = got.detach().cpu()
+        err = metric(got, ref64)
+        e32 = max(metric(r, ref64) for r in (ref32 if isinstance(ref32, (list, tuple)) else [ref32]))
+        lim = self.limit(e32) if lim is None else lim
+        self.log.rows.append(dict(case=self.case, tensor=name, error=err, e32=e32, ratio=(err / e32 if e32 > 0 else None),
+                                  limit=lim))
+        print('%s %s: error %.3e e32 %.3e limit %.3e' % (self.case, name, err, e32, lim))
+        if not err <= lim:
+            self.failed.append('%s %s: error %.3e > limit %.3e (e32 %.3e)' % (self.case, name, err, lim, e32))
+        return lim
+
+    def exact(self, name, got, want):
+        ok = torch.equal(got.detach().cpu(), want)
+        self.log.rows.append(dict(case=self.case, tensor=name, error=0.0 if ok else 1.0, e32=0.0, ratio=None, limit=0.0))
+        if not ok:
+            self.failed.append('%s %s: not bit-identical to the float32 restatement' % (self.case, name))
+
+    def done(self):
+        self.flush()
+        assert not self.failed, '; '.join(self.failed)
+
+
 # ------------------------------------------------------------------------------------------------------- references
 def rand(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale

@@ -13,7 +13,6 @@ asserted.
 
 The runners take the library and the device as parameters: tests/test_mask_fixture_cpu.py passes CPU stand-ins with one
 planted defect each."""
-import json
 import os
 
 import pytest
@@ -26,7 +25,9 @@ from test_model_gpu import OUT as REPORT_DIR
 
 pytestmark = pytest.mark.gpu
 OUT = os.path.join(REPORT_DIR, 'mask_abi_rows.jsonl')
-ROWS = []
+LOG = ah.RowLog(OUT)
+ROWS = LOG.rows
+call, untouched, _bits = ah.call, ah.untouched, ah.bits      # the guarded call and its helpers live in abi_harness.py
 
 
 @pytest.fixture(autouse=True)
@@ -36,71 +37,18 @@ def _dump():
 
 
 def flush():
-    if ROWS:
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        with open(OUT, 'a') as f:
-            for r in ROWS:
-                f.write(json.dumps(r) + '\n')
-        del ROWS[:]
+    LOG.flush()
 
 
 def _lib():
     return ah.raw_lib()
 
 
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def call(lib, dev, fn, specs, args, expect=0):
-    """One guarded call: ``args(P)`` builds the argument list from the arena's address function.  Checks the return
-    code, every band and that no input changed; returns the arena."""
-    ar = ah.Arena(dev, specs)
-    rc = getattr(lib, fn)(*args(ar.ptr))
-    ah._sync(dev)
-    assert rc == expect, '%s returned %d, expected %d (%s)' % (fn, rc, expect, lib.him_last_error())
-    bad = ar.guard_failures()
-    assert not bad, '%s: %s' % (fn, '; '.join(bad))
-    for name, s in specs.items():
-        if s[0] == 'in':
-            assert torch.equal(_bits(ar.t[name]), _bits(s[1])), '%s wrote its input %s' % (fn, name)
-    return ar
-
-
-def untouched(ar, specs):
-    """After a refused call: fresh outputs and the workspace still hold the NaN bytes, prefilled outputs their prefill."""
-    for name, s in specs.items():
-        if s[0] == 'ws' or (s[0] == 'out' and s[2] is None):
-            assert bool((ar.t[name].view(torch.uint8) == ah.NAN_BYTE).all()), name
-        elif s[0] == 'out':
-            assert torch.equal(_bits(ar.t[name]), _bits(s[2])), name
-
-
-class Checks(object):
-    """Collects the rows of one case; ``done()`` asserts after every row has been reported."""
+class Checks(ah.Checks):
+    """abi_harness.Checks on this module's rows, with mask_fixture's metric and limit."""
 
     def __init__(self, case):
-        self.case, self.failed = case, []
-
-    def row(self, name, got, ref64, ref32, metric=fx.rel_err, lim=None):
-        got = got.detach().cpu()
-        err, e32 = metric(got, ref64), metric(ref32, ref64)
-        lim = fx.limit(e32) if lim is None else lim
-        ROWS.append(dict(case=self.case, tensor=name, error=err, e32=e32, ratio=(err / e32 if e32 > 0 else None), limit=lim))
-        print('%s %s: error %.3e e32 %.3e limit %.3e' % (self.case, name, err, e32, lim))
-        if not err <= lim:
-            self.failed.append('%s %s: error %.3e > limit %.3e (e32 %.3e)' % (self.case, name, err, lim, e32))
-        return lim
-
-    def exact(self, name, got, want):
-        ok = torch.equal(got.detach().cpu(), want)
-        ROWS.append(dict(case=self.case, tensor=name, error=0.0 if ok else 1.0, e32=0.0, ratio=None, limit=0.0))
-        if not ok:
-            self.failed.append('%s %s: not bit-identical to the float32 restatement' % (self.case, name))
-
-    def done(self):
-        flush()
-        assert not self.failed, '; '.join(self.failed)
+        ah.Checks.__init__(self, case, LOG, flush=lambda: flush(), metric=fx.rel_err, limit=fx.limit)
 
 
 def _st(dev):
