@@ -959,6 +959,53 @@ int him_boundary_stats(const void* src, int kind, int B, int H, int W, const int
 int him_label_ids(const float* src, int pred_kind, int B, int C, int H, int W, int* ids, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Boundary-weighted and surface losses (the reference ships none): the box2mask trainer's reconstruction terms with a
+ * weight that peaks on the outlines of the ground truth, and a signed-distance term on the object probability.  The
+ * training-side counterpart of the boundary metrics above: every call reads int32 squared-distance planes as him_edt
+ * writes them.  Everything on `stream`, no host synchronisation, no atomics, results bit-identical from run to run.
+ *
+ * Weight of a position with squared distance d2:  w = 1 + amp * exp(-d2 / (2 sigma^2)), and w = 1 exactly where
+ * d2 == HIM_EDT_NONE (tested, not left to underflow); a boundary pixel (d2 == 0) weighs exactly 1 + amp.  fp32.
+ *
+ * him_bw_nll: him_masked_nll with that weight.  logp (B,C,hw), label / mask (B,hw) as there, dist2 (B,hw): one
+ *   HIM_EDT_ANY_BOUNDARY job per sample over the ground-truth label plane.  Valid positions: mask >= 0.5 and
+ *   0 <= (int)label < C.  out2 = {sum_valid w * -logp[label] / sum_valid w, sum_valid w}; nothing valid gives 0/0 = nan,
+ *   as the unweighted loss.  bwd: dlogp[b][c][i] = -g * w_i / sum_w at c = label_i on valid positions, 0 elsewhere;
+ *   sum_w is out2 + 1 of the forward.
+ * him_bw_pair: the mean of him_bce_mean_fwd, kind 0: -(t max(log p, -100) + (1 - t) max(log(1 - p), -100)), or of
+ *   him_l1_mean_fwd, kind 1: |p - t|, with that weight, over n positions: out2 = {sum w l / sum w, sum w}.  dist2 (n): one
+ *   HIM_EDT_ANY_BOUNDARY job per sample over t.  bwd: the derivative of him_bce_mean_bwd ((p - t) / max(p (1 - p), 1e-12))
+ *   or of him_l1_mean_bwd (the sign of p - t, 0 at p == t) times g * w_i / sum_w.
+ * him_surface, after Kervadec et al., "Boundary loss for highly unbalanced segmentation", MIDL 2019: with
+ *   d2_fg / d2_bg (B,H,W) the HIM_EDT_EQUALS 1 / HIM_EDT_EQUALS 0 distances over t, phi = +sqrt(d2_fg) where t < 0.5,
+ *   -sqrt(d2_bg) where t >= 0.5, 0 where the distance it needs is HIM_EDT_NONE (an empty or a full mask).
+ *   out[0] = sum phi * p / (B*H*W * sqrt(H^2 + W^2));  bwd: dp = g * phi / (B*H*W * sqrt(H^2 + W^2)).
+ *
+ * The backward calls recompute w / phi from the distance planes: no weight plane is ever stored.  amp and sigma of a
+ * backward call are those of its forward.
+ * Kernel layout.  Forward: 256-thread workgroups on a fixed grid of at most 64, a grid-stride loop with fp32 sums per
+ *   thread, the workgroup's two sums added in double (block_sum_f64) and written to the workgroup's own workspace slot; a
+ *   second launch of one workgroup adds the slots in slot order in double and writes fp32.  Backward: one element per
+ *   thread and trip of a grid-stride loop, coalesced.
+ * ws: him_bw_loss_ws() bytes, 8-byte aligned; every slot that is read is written by the call first.
+ * HIM_E_INVALID before any launch, outputs untouched: a NULL pointer, B, C, hw, H, W or n < 1, kind outside {0, 1},
+ *   amp < 0, sigma <= 0, a non-finite amp or sigma, a workspace not aligned to 8 bytes; HIM_E_WORKSPACE for a short one.
+ * ------------------------------------------------------------------------------------------- */
+size_t him_bw_loss_ws(void);
+int him_bw_nll_fwd(const float* logp, const float* label, const float* mask, const int* dist2, int B, int C, int hw,
+                   float amp, float sigma, float* out2, void* ws, size_t ws_bytes, void* stream);
+int him_bw_nll_bwd(const float* label, const float* mask, const int* dist2, const float* g, const float* sum_w, float amp,
+                   float sigma, float* dlogp, int B, int C, int hw, void* stream);
+int him_bw_pair_fwd(const float* p, const float* t, const int* dist2, size_t n, int kind, float amp, float sigma,
+                    float* out2, void* ws, size_t ws_bytes, void* stream);
+int him_bw_pair_bwd(const float* p, const float* t, const int* dist2, size_t n, int kind, const float* g,
+                    const float* sum_w, float amp, float sigma, float* dp, void* stream);
+int him_surface_fwd(const float* p, const float* t, const int* d2_fg, const int* d2_bg, int B, int H, int W, float* out,
+                    void* ws, size_t ws_bytes, void* stream);
+int him_surface_bwd(const float* t, const int* d2_fg, const int* d2_bg, int B, int H, int W, const float* g, float* dp,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Feathered canvas composite (the reference ships none: its paste_canvas replaces the whole output window as a hard
  * rectangle).  The image paste of a joint edit with a matte: full strength on and near the pixels the layout edit
  * changed, fading with the exact Euclidean distance to them, and fading towards every side of the paste window that has

@@ -156,6 +156,13 @@ _SIGS = {
     'him_boundary_stats_workspace': (c_size_t, [c_int, c_int, c_int]),
     'him_boundary_stats': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, c_size_t, P]),
     'him_label_ids': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'him_bw_loss_ws': (c_size_t, []),
+    'him_bw_nll_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, c_size_t, P]),
+    'him_bw_nll_bwd': (c_int, [P, P, P, P, P, c_float, c_float, P, c_int, c_int, c_int, P]),
+    'him_bw_pair_fwd': (c_int, [P, P, P, c_size_t, c_int, c_float, c_float, P, P, c_size_t, P]),
+    'him_bw_pair_bwd': (c_int, [P, P, P, c_size_t, c_int, P, P, c_float, c_float, P, P]),
+    'him_surface_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'him_surface_bwd': (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     'him_canvas_changed': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     'him_canvas_paste_blend_v': (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int,
                                          c_int, P, P]),

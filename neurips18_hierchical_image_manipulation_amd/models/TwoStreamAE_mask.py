@@ -28,7 +28,9 @@ DEFAULTS = dict(label_nc=35, output_nc=35, num_layers=3, conv_dim=64, conv_size=
                 which_stream='obj_context', cond_in='ctx_obj', use_gan=True, which_gan='patch_multiscale', gan_weight=0.1,
                 rec_weight=1.0, use_output_gate=True, ndf=64, num_layers_D=3, objReconLoss='bce', use_ganFeat_loss=True,
                 lambda_feat=1.0, lr=0.0002, beta1=0.5, beta2=0.999, lr_control=False, no_comb=True, isTrain=True,
-                gpu_ids=[0], checkpoints_dir='./checkpoints', name='box2mask', niter=400, niter_decay=0)
+                gpu_ids=[0], checkpoints_dir='./checkpoints', name='box2mask', niter=400, niter_decay=0,
+                # additions of this build (options.BOUNDARY_ATTRS): all three off = the reference's step
+                boundary_weight=0.0, boundary_sigma=5.0, surface_weight=0.0)
 
 
 def complete(opt):
@@ -48,9 +50,22 @@ class TwoStreamAE_mask(BaseModel):
     def name(self):
         return 'TwoStreamAE_mask'
 
-    def __init__(self, opt):
+    def __init__(self, opt, **boundary):
+        """``boundary``: boundary_weight / boundary_sigma / surface_weight, overriding the attributes of ``opt``."""
         opt = complete(opt)
         super().__init__(opt)
+        unknown = set(boundary) - {'boundary_weight', 'boundary_sigma', 'surface_weight'}
+        if unknown:
+            raise TypeError('TwoStreamAE_mask: unexpected keyword arguments %s' % sorted(unknown))
+        # --boundary_weight A > 0: both reconstruction terms weigh a position by 1 + A exp(-d^2 / (2 boundary_sigma^2)), d
+        # its distance to the nearest outline of the ground truth; --surface_weight S > 0 adds S * ops.surface_loss
+        self.boundary_weight = float(boundary.get('boundary_weight', opt.boundary_weight))
+        self.boundary_sigma = float(boundary.get('boundary_sigma', opt.boundary_sigma))
+        self.surface_weight = float(boundary.get('surface_weight', opt.surface_weight))
+        if not self.boundary_weight >= 0.0 or not self.boundary_sigma > 0.0 or not self.surface_weight >= 0.0:
+            raise ValueError('box2mask: --boundary_weight >= 0, --boundary_sigma > 0, --surface_weight >= 0, got %r, %r, %r'
+                             % (self.boundary_weight, self.boundary_sigma, self.surface_weight))
+        self.loss_surface = None
         # every value the parser offers for these flags runs (round 6); what the reference itself cannot run fails here
         if opt.cond_in not in ('obj', 'ctx', 'ctx_obj'):
             raise NotImplementedError('--cond_in [%s]: obj | ctx | ctx_obj (reference construct_input_cond)' % opt.cond_in)
@@ -145,7 +160,13 @@ class TwoStreamAE_mask(BaseModel):
         label = self._dev(label_map)
         zero = torch.zeros((), device=self.device)
         obj_gt = self._dev(mask_obj_inst)
-        loss_comb = ops.masked_nll(comb_prob, label, gate) if 'context' in self.which_stream else zero      # :190-191
+        bw = self.boundary_weight
+        if 'context' not in self.which_stream:
+            loss_comb = zero
+        elif bw > 0.0:
+            loss_comb = ops.boundary_weighted_nll(comb_prob, label, gate, bw, self.boundary_sigma)
+        else:
+            loss_comb = ops.masked_nll(comb_prob, label, gate)                                              # :190-191
         loss_obj = zero
         if 'obj' not in self.which_stream:
             obj_prob = torch.zeros_like(obj_gt)       # a constant stands in for the object stream (reference :280-281)
@@ -153,7 +174,13 @@ class TwoStreamAE_mask(BaseModel):
         if 'obj' in self.which_stream and self.objReconLoss is not None:                                    # :192-195
             if self.use_output_gate:
                 obj_prob = ops.mul_mask(obj_prob, gate)
-            loss_obj = (ops.l1_mean if self.objReconLoss == 'l1' else ops.bce_mean)(obj_prob, obj_gt)
+            if bw > 0.0:
+                weighted = ops.boundary_weighted_l1 if self.objReconLoss == 'l1' else ops.boundary_weighted_bce
+                loss_obj = weighted(obj_prob, obj_gt, bw, self.boundary_sigma)     # one transform of obj_gt per step
+            else:
+                loss_obj = (ops.l1_mean if self.objReconLoss == 'l1' else ops.bce_mean)(obj_prob, obj_gt)
+            if self.surface_weight > 0.0:
+                self.loss_surface = ops.surface_loss(obj_prob, obj_gt)
         loss_G_GAN, loss_D, loss_feat = zero, zero, torch.zeros(1, device=self.device)
         if self.use_gan:
             m = gate if self.use_output_gate else None
@@ -172,6 +199,8 @@ class TwoStreamAE_mask(BaseModel):
             with frozen_params():
                 loss_G_GAN = self._gan(self.netD(ops.cat_channels([obj_prob, cond], m, 1)), True)
         loss_G = loss_obj + opt.rec_weight * loss_comb + opt.gan_weight * loss_G_GAN
+        if self.surface_weight > 0.0 and self.loss_surface is not None:
+            loss_G = loss_G + self.surface_weight * self.loss_surface
         if self.use_gan and opt.lr_control:
             # reference :229-245 with the predicate of Discriminator_NET.py:190-211 evaluated ON THE DEVICE (the
             # reference reads three losses back to the host every step): loss_G / loss_D are scaled by g_lr / d_lr in
@@ -196,6 +225,8 @@ class TwoStreamAE_mask(BaseModel):
         # [comb_recon_label, obj_recon_label] as train_box2mask.py:70-71 reads them (the label map is an int64 arg-max map)
         comb_label = (self._comb_label(comb_prob.detach(), label, gate) if comb_prob is not None
                       else torch.zeros_like(gate))          # reference :278-279 without the context stream
+        if self.loss_surface is not None:
+            self.loss_surface = self.loss_surface.detach()
         return [loss_comb.detach(), loss_obj.detach(), 0, loss_G_GAN.detach(), loss_D.detach(), loss_feat.detach()], \
                [comb_label, obj_recon_label]
 

@@ -2957,6 +2957,189 @@ def label_ids(pred, pred_kind):
     return ids
 
 
+# -- boundary-weighted and surface losses (include/him.h "Boundary-weighted and surface losses") ------------------------
+def _bw_args(what, amp, sigma):
+    amp, sigma = float(amp), float(sigma)
+    if not (amp >= 0.0 and amp != float('inf')) or not (sigma > 0.0 and sigma != float('inf')):
+        raise ValueError('%s: amp >= 0 and sigma > 0, both finite, got amp=%r sigma=%r' % (what, amp, sigma))
+    return amp, sigma
+
+
+def _bw_planes(what, shape, **ts):
+    """The named fp32 device tensors of ``shape``, contiguous; ValueError for anything else."""
+    out = []
+    for name, t in ts.items():
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError('%s: %s must be a device tensor' % (what, name))
+        if t.dtype != torch.float32:
+            raise ValueError('%s: %s is %s, not float32' % (what, name, t.dtype))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s: %s is %s, expected %s' % (what, name, tuple(t.shape), tuple(shape)))
+        out.append(t.contiguous())
+    return out
+
+
+def _bw_dist(what, d, shape, device):
+    if not torch.is_tensor(d) or not d.is_cuda or d.dtype != torch.int32 or tuple(d.shape) != tuple(shape) \
+            or d.device != device:
+        raise ValueError('%s: a distance plane must be a %s int32 tensor on the device of the input' % (what, tuple(shape)))
+    return d.contiguous()
+
+
+def boundary_dist2(planes):
+    """int32 (B,H,W): squared distance of every pixel to the nearest class boundary of its own id plane (``planes``:
+    (B,1,H,W) or (B,H,W) integral ids, fp32 included) -- one 'any_boundary' job per sample over the whole plane;
+    ``EDT_NONE`` on a plane of one value."""
+    return distance_transform(planes, rule='any_boundary')[0]
+
+
+def surface_dists(t):
+    """``(d2_fg, d2_bg)``, int32 (B,H,W) each: squared distances to the nearest pixel with ``t == 1`` and with ``t == 0``
+    of the 0/1 mask ``t`` ((B,1,H,W) or (B,H,W)), two 'equals' jobs per sample in one transform."""
+    t = _edt_planes(t, 'surface_dists')
+    B, H, W = t.shape
+    d2 = distance_transform(t, jobs=edt_jobs(B, [0, 1], 'equals', t.device))[0].view(B, 2, H, W)
+    return d2[:, 1].contiguous(), d2[:, 0].contiguous()
+
+
+def _bw_ws(like):
+    nb = lib.him_bw_loss_ws()
+    return torch.empty(max((int(nb) + 7) // 8, 1), dtype=torch.float64, device=like.device), nb
+
+
+class _BWNLL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logp, label, mask, dist2, amp, sigma):
+        ctx.set_materialize_grads(False)
+        B, Cn, H, W = logp.shape
+        with torch.cuda.device(logp.device):
+            out2 = torch.empty(2, dtype=torch.float32, device=logp.device)
+            ws, nb = _bw_ws(logp)
+            lib.him_bw_nll_fwd(_p(logp), _p(label), _p(mask), _p(dist2), B, Cn, H * W, amp, sigma, _p(out2), _p(ws), nb,
+                               _stream())
+        ctx.label, ctx.mask, ctx.dist2, ctx.sum_w = label, mask, dist2, out2[1:2]
+        ctx.shape, ctx.amp, ctx.sigma = (B, Cn, H, W), amp, sigma
+        return out2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None
+        B, Cn, H, W = ctx.shape
+        g = g.contiguous()
+        with torch.cuda.device(g.device):
+            d = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+            lib.him_bw_nll_bwd(_p(ctx.label), _p(ctx.mask), _p(ctx.dist2), _p(g), _p(ctx.sum_w), ctx.amp, ctx.sigma, _p(d),
+                               B, Cn, H * W, _stream())
+        return d, None, None, None, None, None
+
+
+def boundary_weighted_nll(logp, label, mask, amp, sigma, dist2=None):
+    """``masked_nll`` with the weight ``1 + amp * exp(-d2 / (2 sigma^2))`` on every valid position, d2 the squared
+    distance to the nearest class boundary of the ground-truth ``label`` plane (weight 1 on a plane of one class):
+    ``sum w * -logp[label] / sum w`` over the positions with ``mask >= 0.5`` and an id in ``0..C-1``.  ``logp`` (B,C,H,W),
+    ``label`` / ``mask`` (B,1,H,W); ``dist2``: the int32 (B,H,W) result of ``boundary_dist2(label)`` to share one
+    transform, None computes it.  No gradient flows into the targets or through the distances."""
+    what = 'boundary_weighted_nll'
+    amp, sigma = _bw_args(what, amp, sigma)
+    if not torch.is_tensor(logp) or logp.dim() != 4:
+        raise ValueError('%s: logp must be a (B, C, H, W) device tensor' % what)
+    B, _, H, W = logp.shape
+    (logp,) = _bw_planes(what, logp.shape, logp=logp)
+    label, mask = _bw_planes(what, (B, 1, H, W), **{k: v.detach() if torch.is_tensor(v) else v
+                                                    for k, v in (('label', label), ('mask', mask))})
+    dist2 = boundary_dist2(label) if dist2 is None else _bw_dist(what, dist2, (B, H, W), logp.device)
+    return _BWNLL.apply(logp, label, mask, dist2, amp, sigma)
+
+
+class _BWPair(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, dist2, kind, amp, sigma):
+        ctx.set_materialize_grads(False)
+        with torch.cuda.device(p.device):
+            out2 = torch.empty(2, dtype=torch.float32, device=p.device)
+            ws, nb = _bw_ws(p)
+            lib.him_bw_pair_fwd(_p(p), _p(t), _p(dist2), p.numel(), kind, amp, sigma, _p(out2), _p(ws), nb, _stream())
+        ctx.p, ctx.t, ctx.dist2, ctx.sum_w, ctx.kind, ctx.amp, ctx.sigma = p, t, dist2, out2[1:2], kind, amp, sigma
+        return out2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None
+        g = g.contiguous()
+        with torch.cuda.device(g.device):
+            dp = torch.empty_like(ctx.p)
+            lib.him_bw_pair_bwd(_p(ctx.p), _p(ctx.t), _p(ctx.dist2), ctx.p.numel(), ctx.kind, _p(g), _p(ctx.sum_w), ctx.amp,
+                                ctx.sigma, _p(dp), _stream())
+        return dp, None, None, None, None, None
+
+
+def _bw_pair(what, kind, p, t, amp, sigma, dist2):
+    amp, sigma = _bw_args(what, amp, sigma)
+    if not torch.is_tensor(p) or p.dim() != 4 or p.shape[1] != 1:
+        raise ValueError('%s: p must be a (B, 1, H, W) device tensor' % what)
+    p, t = _bw_planes(what, p.shape, p=p, t=t.detach() if torch.is_tensor(t) else t)
+    B, _, H, W = p.shape
+    dist2 = boundary_dist2(t) if dist2 is None else _bw_dist(what, dist2, (B, H, W), p.device)
+    return _BWPair.apply(p, t, dist2, kind, amp, sigma)
+
+
+def boundary_weighted_bce(p, t, amp, sigma, dist2=None):
+    """``bce_mean`` with the weight ``1 + amp * exp(-d2 / (2 sigma^2))``, d2 the squared distance to the outline of the
+    0/1 mask ``t``: ``sum w * bce / sum w`` over all positions.  ``p``, ``t`` (B,1,H,W); ``dist2``: the int32 (B,H,W)
+    result of ``boundary_dist2(t)`` to share one transform, None computes it."""
+    return _bw_pair('boundary_weighted_bce', 0, p, t, amp, sigma, dist2)
+
+
+def boundary_weighted_l1(p, t, amp, sigma, dist2=None):
+    """``l1_mean`` with the weight of ``boundary_weighted_bce``."""
+    return _bw_pair('boundary_weighted_l1', 1, p, t, amp, sigma, dist2)
+
+
+class _Surface(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, d2_fg, d2_bg):
+        ctx.set_materialize_grads(False)
+        B, _, H, W = p.shape
+        with torch.cuda.device(p.device):
+            out = torch.empty((), dtype=torch.float32, device=p.device)
+            ws, nb = _bw_ws(p)
+            lib.him_surface_fwd(_p(p), _p(t), _p(d2_fg), _p(d2_bg), B, H, W, _p(out), _p(ws), nb, _stream())
+        ctx.t, ctx.d2_fg, ctx.d2_bg, ctx.shape = t, d2_fg, d2_bg, (B, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        B, H, W = ctx.shape
+        g = g.contiguous()
+        with torch.cuda.device(g.device):
+            dp = torch.empty_like(ctx.t)
+            lib.him_surface_bwd(_p(ctx.t), _p(ctx.d2_fg), _p(ctx.d2_bg), B, H, W, _p(g), _p(dp), _stream())
+        return dp, None, None, None
+
+
+def surface_loss(p, t, dists=None):
+    """The surface term of Kervadec et al. on the probability ``p`` against the 0/1 mask ``t`` (both (B,1,H,W)):
+    ``sum phi * p / (B*H*W * sqrt(H^2 + W^2))`` with phi the signed distance to the outline of ``t`` -- ``+sqrt(d2_fg)``
+    outside the mask, ``-sqrt(d2_bg)`` inside, 0 for an empty or a full mask.  Negative where the prediction sits inside
+    the mask; lowering it pulls the probability mass towards the mask and lowers the surface distance.  ``dists``: the
+    pair of ``surface_dists(t)`` to share one transform, None computes it."""
+    what = 'surface_loss'
+    if not torch.is_tensor(p) or p.dim() != 4 or p.shape[1] != 1:
+        raise ValueError('%s: p must be a (B, 1, H, W) device tensor' % what)
+    p, t = _bw_planes(what, p.shape, p=p, t=t.detach() if torch.is_tensor(t) else t)
+    B, _, H, W = p.shape
+    if dists is None:
+        dists = surface_dists(t)
+    if not isinstance(dists, (tuple, list)) or len(dists) != 2:
+        raise ValueError('%s: dists must be the pair (d2_fg, d2_bg)' % what)
+    d2_fg, d2_bg = (_bw_dist(what, d, (B, H, W), p.device) for d in dists)
+    return _Surface.apply(p, t, d2_fg, d2_bg)
+
+
 # -- panoptic matching: segments, overlaps, unique matches, per-class tp / fp / fn (include/him.h "Panoptic matching") ---
 PQ_OVERFLOW, PQ_ID_RANGE, PQ_CLS_RANGE, PQ_MIXED, PQ_CCL = 1, 2, 4, 8, 16
 _SEG_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}

@@ -100,6 +100,10 @@ DIFFAUG_FLAGS = [('diffaug', str, ''), ('diffaug_seed', int, 0), ('diffaug_trans
 EMA_ATTRS = (('ema_decay', float, 0.0), ('use_ema', 'flag', False))
 # the gradient-guard settings travel the same way
 GUARD_ATTRS = (('clip_grad_norm', float, 0.0), ('skip_nonfinite', 'flag', False))
+# boundary-weighted reconstruction and the surface term of the box2mask TRAINING parser only (models/TwoStreamAE_mask.py,
+# DESIGN.md 7q): --boundary_weight A > 0 weighs both reconstruction terms by 1 + A exp(-d^2 / (2 boundary_sigma^2)) around
+# the outlines of the ground truth, --surface_weight S > 0 adds S times the signed-distance term; 0 = off, the step as it was
+BOUNDARY_ATTRS = (('boundary_weight', float, 0.0), ('boundary_sigma', float, 5.0), ('surface_weight', float, 0.0))
 
 
 def _take_attr_flags(argv, attrs):
@@ -182,6 +186,7 @@ class BoxToMaskOptions(MaskToImageOptions):
 class BoxToMaskTrainOptions(BoxToMaskOptions):
     isTrain = True
     tables = [BOX2MASK_BASE_FLAGS, BOX2MASK_TRAIN_FLAGS]
+    attrs = EMA_ATTRS + GUARD_ATTRS + BOUNDARY_ATTRS
 
 
 class BoxToMaskTestOptions(BoxToMaskOptions):
