@@ -1046,6 +1046,60 @@ int him_canvas_paste_blend_v(const unsigned char* tmp, const int* first, const i
                              int reach, int profile, float* matte, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Layout edits (the reference ships none: its public path only adds an object): take an instance out of a (label,
+ * instance) canvas pair and fill the hole, and write an instance of one pair into another at another place and size.
+ * Everything on `stream`, no host synchronisation, integer work, integer atomics only (add / or / min / max): results
+ * bit-identical from run to run.  Planes are (H,W) of kind 0 uint8 / 1 int32 / 2 int64 / 3 fp32 holding integral ids
+ * (him_edt's kinds), label and instance plane each of its own kind; outputs have the kind of their input.  A class bit
+ * table is uint32 words on the device, class c being bit (c & 31) of word c >> 5, (n_class + 31) / 32 words.
+ *
+ * him_layout_erase: R = {p : region[p] != 0} when region (uint8 (H,W)) is given, else {p : inst[p] == id}.  Seeds
+ *   S = {p not in R : 0 <= label[p] < n_class and label[p] in fill}.  s(p) = the seed nearest to p in squared Euclidean
+ *   distance, among equidistant seeds the smallest y * W + x: him_edt's feature transform, run by this call on a seed
+ *   plane it writes into the workspace (the transform is not restated).  For p in R with 0 <= label[p] < n_class:
+ *   label_out[p] = label[s(p)], inst_out[p] = inst[s(p)]; every other pixel is copied.  changed[p] (uint8 (H,W)) =
+ *   label_out[p] != label[p].
+ *   status: 4 ints written by the device: [|R|, |S|, pixels whose label changed, flags].  HIM_LAYOUT_NO_SEED: S is empty,
+ *           both planes come out as copies, changed is zero.  HIM_LAYOUT_CLASS_RANGE: a label outside [0, n_class) (or
+ *           not integral) was seen; such pixels are never seeds and are never rewritten.
+ *   ws:     him_layout_erase_workspace(H, W) bytes (0 for a refused shape), 16-byte aligned; written before it is read.
+ *   HIM_E_INVALID before any launch: H or W outside 1..16384, an unknown kind, n_class outside 1..65536, a NULL label /
+ *   inst / fill / label_out / inst_out / changed / status, a pointer not aligned to its element, an output that overlaps
+ *   an input or another output.  HIM_E_WORKSPACE: ws NULL or short.
+ *   Kernel layout: init (one thread), the seed pass (grid-stride, a pixel per thread and trip: region test, table
+ *   lookup, the seed byte, the copies, |R| and the range flag with one atomic per wave), him_edt's three launches, the
+ *   gather pass (grid-stride; reads both planes at nearest[p], counts the changed pixels, copies the seed count).
+ *
+ * him_layout_place: the mask Rs = {p in the source box [sx0, sy0, sx1, sy1) : inst_src[p] == id} of an (Hs,Ws) plane,
+ *   resampled to the destination box [dx0, dy0, dx1, dy1) of an (Hd,Wd) pair: destination pixel (x, y) of the box reads
+ *   source pixel (sx0 + xs[x - dx0], sy0 + ys[y - dy0]); xs (dx1 - dx0 ints) and ys (dy1 - dy0 ints) are index tables on
+ *   the device, Pillow's NEAREST tables for a bit-identical Image.resize of the cropped mask (an entry outside the source
+ *   box reads as unset).  Where the resampled mask is set and the pixel lies inside the canvas (the box may hang over any
+ *   edge): if protect is given and the pixel's current class is in it, the pixel is counted as blocked and left alone;
+ *   otherwise label_dst = cls, inst_dst = new_id and, with changed (uint8 (Hd,Wd), may be NULL) given, changed = 1.
+ *   Nothing else is written; label_dst / inst_dst are edited in place.  inst_src and inst_dst share inst_kind.
+ *   status: 6 ints written by the device: [pixels written, pixels blocked, xmin, ymin, xmax, ymax of the written
+ *           pixels], zero-based inclusive as him_inst_summary's rows; [2147483647, 2147483647, -1, -1] when none.
+ *   HIM_E_INVALID before any launch: a plane side outside 1..16384, an unknown kind, a source box that is empty or not
+ *   inside its plane, an empty destination box or one beyond +-2^20, n_class outside 1..65536 with protect given, cls /
+ *   new_id that the planes' kinds cannot hold (uint8: 0..255, fp32: |v| <= 2^24), a NULL inst_src / xs / ys / label_dst /
+ *   inst_dst / status, a misaligned pointer, inst_src overlapping a destination plane (a move reads the mask from the
+ *   original canvas and writes onto the erased copy), destination planes overlapping each other.
+ *   Kernel layout: status init; a 256-thread workgroup per tile of 64 columns x 4 rows of the clipped box, lane =
+ *   column, a pixel per thread; wave reductions in front of the atomics.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_LAYOUT_NO_SEED 1
+#define HIM_LAYOUT_CLASS_RANGE 2
+size_t him_layout_erase_workspace(int H, int W);
+int him_layout_erase(const void* label, int label_kind, const void* inst, int inst_kind, const unsigned char* region,
+                     int id, int H, int W, const unsigned int* fill, int n_class, void* label_out, void* inst_out,
+                     unsigned char* changed, int* status, void* ws, size_t ws_bytes, void* stream);
+int him_layout_place(const void* inst_src, int inst_kind, int Hs, int Ws, int id, int sx0, int sy0, int sx1, int sy1,
+                     const int* xs, const int* ys, void* label_dst, int label_kind, void* inst_dst, int Hd, int Wd, int dx0,
+                     int dy0, int dx1, int dy1, int cls, int new_id, const unsigned int* protect, int n_class,
+                     unsigned char* changed, int* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Set-level metrics (the reference ships none): the sliced Wasserstein distance between the Laplacian-pyramid patches of
  * two SETS of images (Karras et al., "Progressive Growing of GANs", ICLR 2018, section 5 and its sliced_wasserstein.py).
  * No network, no weights; everything on `stream`, no host synchronisation, no allocation, results bit-identical from

@@ -8,6 +8,8 @@ one ``np.random.uniform``).  Canvases are device tensors: label canvas (1,1,H,W)
 import numpy as np
 import torch
 
+from .. import ops
+from .._cabi import HimError
 from ..data.base_dataset import NEAREST, get_raw_transform_fn
 from ..data.device import ImageTransform
 from ..util.data_util import _blend_args, _paste_image, crop_canvas, paste_canvas
@@ -87,4 +89,120 @@ class JointInference(object):
                 label_before=label_before, label_after=None if label_before is None else label_generated,
                 want_matte=True)
         return img_canvas, input_dict, img_generated
+
+    # -- edits of an object that is already in the scene: the layout edit is ops.layout_erase /
+    # ops.layout_place, the photograph is repainted window by window with gen_image_feathered ---------------------------
+    def _edit_classes(self, fill, things):
+        n_class = int(self.opt_maskgen.label_nc)
+        if fill is None:
+            things = ops.CITYSCAPES_THINGS if things is None else things
+            things = set(int(c) for c in things)
+            fill = tuple(c for c in range(n_class) if c not in things)
+        return tuple(fill), n_class
+
+    def _repaint(self, box, cls, img_canvas, label_before, label_after, opt, feather, reach, profile):
+        bbox = {'bbox': [int(v) for v in box], 'cls': int(cls)}
+        if feather is None:
+            canvas, input_dict, _ = self.gen_image_feathered(bbox, img_canvas, label_after, opt)
+        else:
+            canvas, input_dict, _ = self.gen_image_feathered(bbox, img_canvas, label_after, opt, feather=feather,
+                                                             reach=reach, profile=profile, label_before=label_before)
+        return canvas, input_dict
+
+    def _erase(self, obj, label_original, inst_original, img_original, fill, things, feather, reach, profile):
+        obj_id, box, cls = edit_object(obj)
+        _blend_args(img_original, feather, reach, profile, None if feather is None else label_original,
+                    None if feather is None else label_original, False)
+        fill, n_class = self._edit_classes(fill, things)
+        label_canvas, inst_canvas, _, status = ops.layout_erase(label_original, inst_original, obj_id, fill=fill,
+                                                                n_class=n_class)
+        erase = [int(v) for v in status.cpu().tolist()]
+        if erase[3] & ops.LAYOUT_NO_SEED:
+            raise HimError('JointInference: object %d cannot be removed: no pixel outside it has a class of the fill set %s'
+                           % (obj_id, list(fill)))
+        return obj_id, box, cls, label_canvas, inst_canvas, erase
+
+    def remove_object(self, obj, label_original, inst_original, img_original, opt, *, fill=None, things=None, feather=None,
+                      reach=0, profile='smooth'):
+        """Take the object ``obj`` (an item ``(id, {'bbox', 'cls'})`` of an ``inst_info`` / ``layout_info`` dict's
+        ``'objects'``, or a dict with ``id``, ``bbox``, ``cls``) out of the scene: its pixels take label and instance id of
+        the nearest pixel whose class is in ``fill`` (None: every class of the layout generator's ``label_nc`` that is not
+        in ``things``, by default ``ops.CITYSCAPES_THINGS``), the box table is rebuilt, and the photograph is repainted
+        over the object's box with ``gen_image_feathered`` (``feather`` / ``reach`` / ``profile`` as there; with
+        ``feather`` only pixels near what the edit changed are touched).  -> ``(label_canvas, inst_canvas, img_canvas,
+        info, report)``; ``report``: ``{'erase': [|R|, seeds, changed, flags], 'place': None, 'passes': [input_dict]}``.
+        ``HimError`` when there is nothing to fill from: no canvas with the object still in it is returned."""
+        from ..preprocess import inst_info
+        _, box, cls, label_canvas, inst_canvas, erase = self._erase(obj, label_original, inst_original, img_original, fill,
+                                                                    things, feather, reach, profile)
+        info = inst_info(inst_canvas, label_canvas)
+        img_canvas, input_dict = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach,
+                                               profile)
+        return label_canvas, inst_canvas, img_canvas, info, {'erase': erase, 'place': None, 'passes': [input_dict]}
+
+    def move_object(self, obj, dst_box, label_original, inst_original, img_original, opt, *, fill=None, things=None,
+                    protect=(), new_id=None, feather=None, reach=0, profile='smooth'):
+        """Move ``obj`` to ``dst_box`` (``[xmin, ymin, xmax, ymax]`` inclusive, as ``obj``'s own ``bbox``; another size
+        rescales the mask as Pillow's NEAREST resize would; the box may hang over the canvas): ``remove_object``'s erase on
+        the originals, then the object's original mask is written at ``dst_box`` with its class and ``new_id`` (None: its
+        own id), behind the pixels whose class is in ``protect``.  The photograph is repainted over the vacated box and
+        then, on that result, over the box of the pixels written.  -> as ``remove_object``; ``report['place']``:
+        ``[written, blocked, xmin, ymin, xmax, ymax]``, ``report['passes']`` one ``input_dict`` per repaint."""
+        from ..preprocess import inst_info
+        try:
+            dx0, dy0, dx1, dy1 = (int(v) for v in dst_box)
+        except (TypeError, ValueError):
+            raise ValueError('move_object: dst_box must be [xmin, ymin, xmax, ymax], got %r' % (dst_box,))
+        if dx1 < dx0 or dy1 < dy0:
+            raise ValueError('move_object: dst_box %r is empty' % (dst_box,))
+        obj_id, box, cls, label_e, inst_e, erase = self._erase(obj, label_original, inst_original, img_original, fill,
+                                                               things, feather, reach, profile)
+        label_canvas, inst_canvas, _, status = ops.layout_place(
+            label_e, inst_e, inst_original, obj_id, (box[0], box[1], box[2] + 1, box[3] + 1), (dx0, dy0, dx1 + 1, dy1 + 1),
+            cls, obj_id if new_id is None else new_id, protect=protect)
+        place = [int(v) for v in status.cpu().tolist()]
+        info = inst_info(inst_canvas, label_canvas)
+        img_canvas, first = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach, profile)
+        passes = [first]
+        if place[0] > 0:
+            img_canvas, second = self._repaint(place[2:6], cls, img_canvas, label_original, label_canvas, opt, feather,
+                                               reach, profile)
+            passes.append(second)
+        return label_canvas, inst_canvas, img_canvas, info, {'erase': erase, 'place': place, 'passes': passes}
+
+    def rescale_object(self, obj, scale, label_original, inst_original, img_original, opt, **kw):
+        """``move_object`` to ``scaled_box(obj's bbox, scale)``: the box scaled about its centre."""
+        _, box, _ = edit_object(obj)
+        return self.move_object(obj, scaled_box(box, scale), label_original, inst_original, img_original, opt, **kw)
+
+
+def edit_object(obj):
+    """(id, [xmin, ymin, xmax, ymax], cls) of an ``info['objects']`` item ``(id, {'bbox', 'cls'})`` or of a dict with
+    ``id``, ``bbox`` and ``cls``."""
+    try:
+        if isinstance(obj, dict):
+            obj_id, entry = obj['id'], obj
+        else:
+            obj_id, entry = obj
+        box = [int(v) for v in entry['bbox'][:4]]
+        obj_id, cls = int(obj_id), int(entry['cls'])
+    except (TypeError, ValueError, KeyError, IndexError):
+        raise ValueError("an object is an item (id, {'bbox': [xmin, ymin, xmax, ymax], 'cls': c}) of info['objects'] or a "
+                         "dict with id, bbox and cls, got %r" % (obj,))
+    if len(box) != 4 or box[2] < box[0] or box[3] < box[1]:
+        raise ValueError('object %d: bbox %r is not [xmin, ymin, xmax, ymax]' % (obj_id, box))
+    return obj_id, box, cls
+
+
+def scaled_box(box, scale):
+    """The inclusive box ``[xmin, ymin, xmax, ymax]`` with both sides multiplied by ``scale`` (rounded, at least one
+    pixel) about its centre."""
+    import math
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale <= 0:
+        raise ValueError('scale must be a positive finite number, got %r' % (scale,))
+    x0, y0, x1, y1 = (int(v) for v in box)
+    w, h = x1 - x0 + 1, y1 - y0 + 1
+    w2, h2 = max(1, int(round(w * scale))), max(1, int(round(h * scale)))
+    nx0, ny0 = int(math.floor((x0 + x1 + 1 - w2) / 2.0)), int(math.floor((y0 + y1 + 1 - h2) / 2.0))
+    return [nx0, ny0, nx0 + w2 - 1, ny0 + h2 - 1]
 

@@ -2957,6 +2957,171 @@ def label_ids(pred, pred_kind):
     return ids
 
 
+# -- layout edits: take an instance out and fill the hole, write an instance elsewhere (include/him.h "Layout edits") ----
+LAYOUT_NO_SEED, LAYOUT_CLASS_RANGE = 1, 2
+LAYOUT_MAX_CLASS = 65536
+LAYOUT_MAX_COORD = 1 << 20
+_LAYOUT_WS = {}         # (H, W, device index) -> workspace of him_layout_erase
+_LAYOUT_TABLES = {}     # (class ids, n_class, device index) -> device class bit table
+_LAYOUT_INDEX = {}      # (source length, destination length, device index) -> device NEAREST index table
+_LAYOUT_ID_RANGE = {torch.uint8: (0, 255), torch.int32: (-2 ** 31, 2 ** 31 - 1), torch.int64: (-2 ** 31, 2 ** 31 - 1),
+                    torch.float32: (-2 ** 24, 2 ** 24)}
+
+
+def _layout_plane(t, what):
+    """One (H, W) plane out of the shapes ``_edt_planes`` takes, B = 1."""
+    planes = _edt_planes(t, what)
+    if planes.shape[0] != 1:
+        raise ValueError('%s: one plane at a time (B = 1), got %s' % (what, tuple(t.shape)))
+    return planes[0]
+
+
+def _layout_int(v, what, lo, hi):
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
+        raise ValueError('%s must be an integer in %d..%d, got %r' % (what, lo, hi, v))
+    return int(v)
+
+
+def _layout_classes(classes, n_class, what):
+    try:
+        ids = tuple(sorted(set(int(c) for c in classes)))
+    except (TypeError, ValueError):
+        raise ValueError('%s must be an iterable of class ids' % what)
+    for c in ids:
+        if not 0 <= c < n_class:
+            raise ValueError('%s: class %d outside 0..%d' % (what, c, n_class - 1))
+    return ids
+
+
+def _layout_table(ids, n_class, device):
+    """The device bit table of the class ids over [0, n_class): uint32 words, class c is bit c & 31 of word c >> 5."""
+    import numpy as np
+    key = (ids, n_class, device.index)
+    table = _LAYOUT_TABLES.get(key)
+    if table is None:
+        words = np.zeros((n_class + 31) // 32, np.uint32)
+        for c in ids:
+            words[c >> 5] |= np.uint32(1 << (c & 31))
+        if len(_LAYOUT_TABLES) > 256:
+            _LAYOUT_TABLES.clear()
+        table = _LAYOUT_TABLES[key] = torch.from_numpy(words.view(np.int32)).to(device)
+    return table
+
+
+def _layout_index(src_len, dst_len, device):
+    import numpy as np
+    from .data import resample
+    key = (src_len, dst_len, device.index)
+    tab = _LAYOUT_INDEX.get(key)
+    if tab is None:
+        if len(_LAYOUT_INDEX) > 256:
+            _LAYOUT_INDEX.clear()
+        tab = _LAYOUT_INDEX[key] = torch.from_numpy(np.ascontiguousarray(resample.nearest_table(src_len, dst_len),
+                                                                         np.int32)).to(device)
+    return tab
+
+
+def _layout_box(box, what):
+    try:
+        x0, y0, x1, y1 = (v for v in box)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be [xmin, ymin, xmax, ymax), got %r' % (what, box))
+    x0, y0, x1, y1 = (_layout_int(v, what, -LAYOUT_MAX_COORD, LAYOUT_MAX_COORD) for v in (x0, y0, x1, y1))
+    if x1 <= x0 or y1 <= y0:
+        raise ValueError('%s [%d, %d, %d, %d) is empty' % (what, x0, y0, x1, y1))
+    return x0, y0, x1, y1
+
+
+def layout_erase(label, inst, id=None, *, region=None, fill, n_class):
+    """Take the region R out of a (label, inst) canvas pair: ``(label_out, inst_out, changed, status)`` on the device.
+    R is ``inst == id`` or, given instead, the nonzero pixels of ``region`` (uint8 / bool, one (H, W) plane).  Every
+    pixel of R takes label and instance id of the nearest pixel outside R whose class is in ``fill`` (an iterable of
+    class ids below ``n_class``): exact squared Euclidean distance, the smallest ``y * W + x`` among equidistant ones
+    (``distance_transform``'s rule; the transform is the same kernel).  Everything else is copied.  ``label`` / ``inst``:
+    uint8 / int32 / int64 / integral fp32 device planes, (H, W), (1, H, W) or (1, 1, H, W); the outputs have their dtype
+    and shape.  ``changed``: uint8 (H, W), 1 where the label changed.  ``status``: int32 (4,) [|R|, seeds, changed pixels,
+    flags]; ``LAYOUT_NO_SEED``: no pixel of an allowed class, the outputs are copies; ``LAYOUT_CLASS_RANGE``: a label
+    outside [0, n_class) was seen (never a seed, never rewritten).  Current stream, no host synchronisation, no autograd.
+    The workspace is cached per (H, W) and device: calls of one shape must be queued on one stream at a time."""
+    if (id is None) == (region is None):
+        raise ValueError('layout_erase: give an instance id or a region plane, not both')
+    if region is None:
+        id = _layout_int(id, 'layout_erase: id', -2 ** 31, 2 ** 31 - 1)
+    n_class = _layout_int(n_class, 'layout_erase: n_class', 1, LAYOUT_MAX_CLASS)
+    fill = _layout_classes(fill, n_class, 'layout_erase: fill')
+    lab = _layout_plane(label, 'layout_erase: label')
+    ins = _layout_plane(inst, 'layout_erase: inst')
+    if lab.shape != ins.shape or lab.device != ins.device:
+        raise ValueError('layout_erase: label %s on %s and inst %s on %s differ' % (tuple(lab.shape), lab.device,
+                                                                                 tuple(ins.shape), ins.device))
+    H, W = lab.shape
+    if region is not None:
+        if not torch.is_tensor(region) or not region.is_cuda or region.dtype not in (torch.uint8, torch.bool) or \
+                region.device != lab.device or region.numel() != H * W or tuple(region.shape[-2:]) != (H, W):
+            raise ValueError('layout_erase: region must be a uint8 / bool (%d, %d) plane on the device of label' % (H, W))
+        region = region.detach().contiguous().view(torch.uint8)
+        id = 0
+    table = _layout_table(fill, n_class, lab.device)
+    with torch.cuda.device(lab.device):
+        key = (H, W, torch.cuda.current_device())
+        ws = _LAYOUT_WS.get(key)
+        if ws is None:
+            ws = _LAYOUT_WS[key] = torch.empty(max(int(lib.him_layout_erase_workspace(H, W)), 16), dtype=torch.uint8,
+                                               device=lab.device)
+        label_out, inst_out = torch.empty_like(lab), torch.empty_like(ins)
+        changed = torch.empty((H, W), dtype=torch.uint8, device=lab.device)
+        status = torch.empty(4, dtype=torch.int32, device=lab.device)
+        lib.him_layout_erase(_p(lab), _PRED_KINDS[lab.dtype], _p(ins), _PRED_KINDS[ins.dtype], _p(region), id, H, W,
+                             _p(table), n_class, _p(label_out), _p(inst_out), _p(changed), _p(status), _p(ws), ws.numel(),
+                             _stream())
+    return label_out.reshape(label.shape), inst_out.reshape(inst.shape), changed, status
+
+
+def layout_place(label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_id, *, protect=()):
+    """Write the instance ``id`` of the plane ``inst_src``, cut out by ``src_box`` and resized to ``dst_box`` (both
+    ``[xmin, ymin, xmax, ymax)``), onto copies of the pair ``label_dst`` / ``inst_dst``: ``(label_out, inst_out, changed,
+    status)`` on the device.  The resized mask is bit-identical to Pillow's ``Image.resize(NEAREST)`` of the cropped mask
+    (``data/resample.nearest_table``); ``dst_box`` may hang over the canvas, that part is clipped.  Where the mask is set
+    the pixel becomes class ``cls``, instance ``new_id``, except where its current class is in ``protect``: those stay
+    in front.  ``changed``: uint8 (H, W), 1 on the written pixels.  ``status``: int32 (6,) [written, blocked, xmin, ymin,
+    xmax, ymax of the written pixels, inclusive as ``inst_summary``'s rows; (2^31 - 1, 2^31 - 1, -1, -1) when none].
+    Planes as ``layout_erase`` takes them; ``inst_src`` has the dtype of ``inst_dst``.  Current stream, no host
+    synchronisation, no autograd."""
+    id = _layout_int(id, 'layout_place: id', -2 ** 31, 2 ** 31 - 1)
+    sx0, sy0, sx1, sy1 = _layout_box(src_box, 'layout_place: src_box')
+    dx0, dy0, dx1, dy1 = _layout_box(dst_box, 'layout_place: dst_box')
+    _layout_int(cls, 'layout_place: cls', -2 ** 31, 2 ** 31 - 1)
+    _layout_int(new_id, 'layout_place: new_id', -2 ** 31, 2 ** 31 - 1)
+    prot = _layout_classes(protect, LAYOUT_MAX_CLASS, 'layout_place: protect')
+    n_class = prot[-1] + 1 if prot else 1
+    lab = _layout_plane(label_dst, 'layout_place: label_dst')
+    ins = _layout_plane(inst_dst, 'layout_place: inst_dst')
+    src = _layout_plane(inst_src, 'layout_place: inst_src')
+    if lab.shape != ins.shape or lab.device != ins.device or src.device != lab.device:
+        raise ValueError('layout_place: label_dst %s on %s, inst_dst %s on %s and inst_src on %s differ'
+                         % (tuple(lab.shape), lab.device, tuple(ins.shape), ins.device, src.device))
+    if src.dtype != ins.dtype:
+        raise ValueError('layout_place: inst_src is %s, inst_dst %s' % (src.dtype, ins.dtype))
+    Hd, Wd = lab.shape
+    Hs, Ws = src.shape
+    if sx0 < 0 or sy0 < 0 or sx1 > Ws or sy1 > Hs:
+        raise ValueError('layout_place: src_box [%d, %d, %d, %d) is not inside the %d x %d plane' % (sx0, sy0, sx1, sy1, Ws, Hs))
+    cls = _layout_int(cls, 'layout_place: cls (%s plane)' % lab.dtype, *_LAYOUT_ID_RANGE[lab.dtype])
+    new_id = _layout_int(new_id, 'layout_place: new_id (%s plane)' % ins.dtype, *_LAYOUT_ID_RANGE[ins.dtype])
+    table = _layout_table(prot, n_class, lab.device) if prot else None
+    with torch.cuda.device(lab.device):
+        xs = _layout_index(sx1 - sx0, dx1 - dx0, lab.device)
+        ys = _layout_index(sy1 - sy0, dy1 - dy0, lab.device)
+        label_out, inst_out = lab.clone(), ins.clone()
+        changed = torch.zeros((Hd, Wd), dtype=torch.uint8, device=lab.device)
+        status = torch.empty(6, dtype=torch.int32, device=lab.device)
+        lib.him_layout_place(_p(src), _PRED_KINDS[src.dtype], Hs, Ws, id, sx0, sy0, sx1, sy1, _p(xs), _p(ys),
+                             _p(label_out), _PRED_KINDS[lab.dtype], _p(inst_out), Hd, Wd, dx0, dy0, dx1, dy1, cls, new_id,
+                             _p(table), n_class, _p(changed), _p(status), _stream())
+    return label_out.reshape(label_dst.shape), inst_out.reshape(inst_dst.shape), changed, status
+
+
 # -- boundary-weighted and surface losses (include/him.h "Boundary-weighted and surface losses") ------------------------
 def _bw_args(what, amp, sigma):
     amp, sigma = float(amp), float(sigma)
