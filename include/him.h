@@ -1046,6 +1046,71 @@ int him_canvas_paste_blend_v(const unsigned char* tmp, const int* first, const i
                              int reach, int profile, float* matte, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Seamless canvas composite (the reference ships none): gradient-domain (Poisson) cloning of a patch into the
+ * photograph.  For the 5-point Laplacian on a rectangle the clone of P into O is exactly P + m, m being the discrete
+ * harmonic function ("membrane") whose boundary values are O - P on the window's border.  Everything on `stream`, no host
+ * synchronisation, no atomics, fp64 up to the stored fp32 membrane, results bit-identical from run to run.
+ *
+ * Window and sides: the window is H x W at (x0, y0) of an Hc x Wc canvas; a side is counted as in the feathered
+ *   composite: left iff x0 > 0, right iff x0 + W < Wc, top iff y0 > 0, bottom iff y0 + H < Hc; l, r, t, b in {0,1}.
+ *   The sides mask is l | r << 1 | t << 2 | b << 3.  Ring: the window's first / last row / column on each counted side.
+ *   Interior: rows [t, H - b), columns [l, W - r); ny = H - t - b, nx = W - l - r.  ny < 1 or nx < 1: HIM_E_INVALID.
+ *
+ * Membrane, per channel: P (3,H,W) fp32 is the byte / 255 value the hard paste writes.  g = (double)O - (double)P on ring
+ *   pixels.  For every interior pixel p:   deg(p) m(p) - sum_{q in N(p), q interior} m(q) = sum_{q in N(p), q in ring} g(q)
+ *   N(p): the 4-neighbours of p inside the window, deg(p) = |N(p)|; a neighbour beyond an uncounted side does not exist
+ *   (Neumann); a corner ring pixel is nobody's neighbour.  On the ring m := g.  No side counted: m := 0 and
+ *   HIM_MEMBRANE_NO_SIDE is set in the status.  The dense float64 solve of these equations is the authority.
+ *
+ * Solver: per axis of length n with flags (lo, hi) the orthonormal basis V (n x n, V[j][k], j the pixel, k the mode) is
+ *   the normalised columns of, with eigenvalue lam[k] of the 1-D second difference (j, k = 0..n-1):
+ *     (1,1)  sin(pi (k+1)(j+1) / (n+1))          2 - 2 cos(pi (k+1) / (n+1))
+ *     (0,0)  cos(pi k (2j+1) / (2n))             2 - 2 cos(pi k / n)
+ *     (1,0)  sin(pi (2k+1)(j+1) / (2n+1))        2 - 2 cos(pi (2k+1) / (2n+1))
+ *     (0,1)  sin(pi (2k+1)(n-j) / (2n+1))        as (1,0)
+ *   m = Vy (Bh / (lamy_i + lamx_j)) Vx^T on the interior, Bh = Vy^T B Vx with B the right-hand side above:
+ *     Bh[i][j] = Vy[0][i] (gT . Vx[:,j]) + Vy[ny-1][i] (gB . Vx[:,j]) + (Vy[:,i] . gL) Vx[0][j] + (Vy[:,i] . gR) Vx[nx-1][j]
+ *   (terms of uncounted sides dropped; gT / gB: the ring rows above / below the interior's columns, gL / gR: the ring
+ *   columns beside its rows).  lamy_0 + lamx_0 = 0 only when no side is counted, which never reaches the division.
+ *
+ * him_membrane_basis: V, its transpose Vt and lam (n doubles) of the pair (lo, hi) on the device.  The integer product in
+ *   the sine / cosine argument is reduced modulo the period and folded into the first quarter in integers, then sinpi /
+ *   cospi of the reduced rational: accuracy does not fall with n.  Columns are normalised by the square root of their
+ *   fp64 sum of squares, added in a fixed order.  lam is evaluated as 4 sin^2 of the half angle.  HIM_E_INVALID: a NULL or
+ *   misaligned pointer, V == Vt, n outside 1..2048, a flag outside {0,1}.
+ * him_membrane_ws: bytes of workspace for an H x W window with the given sides mask; 0 for a refused shape.
+ * him_membrane_solve: m (3,H,W) fp32: (float)g on the ring, the membrane on the interior.  Vy / Vyt / lamy: the basis of
+ *   (ny, t, b); Vx / Vxt / lamx: of (nx, l, r); all may be NULL when no side is counted (ws too).
+ *   status: 4 ints written by the device: [sides mask, ny, nx, flags].
+ *   ws: him_membrane_ws bytes, 8-byte aligned; every slot that is read is written by the call first.
+ *   HIM_E_INVALID before any launch, outputs untouched: a NULL canvas / P / m / status or a NULL basis with a side
+ *   counted, a window not inside the canvas, ny or nx < 1 or > 2048, a workspace not aligned to 8 bytes;
+ *   HIM_E_WORKSPACE: ws NULL with a side counted.
+ *   Kernel layout: ring gather (a thread per ring pixel and channel) -> four matrix-vector products (a wave per output,
+ *   fixed-order sums) -> the rank-4 update fused with the division -> a row-major fp64 GEMM run twice, grid z = channel:
+ *   256 threads, a 64 x 64 tile as four waves of 2 x 2 v_mfma_f64_16x16x4_f64 accumulators, K step 16 staged through
+ *   LDS at conflict-free pitches, edge tiles masked, plain vector stores; the second pass narrows to fp32 into m.
+ *
+ * him_canvas_seamless_apply: v = min(max(P + m, 0), 1) (one fp32 add, no contraction).  On the ring the canvas is left
+ *   untouched (P + g is O).  On the interior the canvas becomes O + alpha (v - O) with alpha exactly the matte of
+ *   him_canvas_paste_blend_v (same feather, reach, profile, dist2, same arithmetic); feather == 0: alpha = 1 (dist2 must
+ *   be NULL and reach 0).  alpha == 1 writes v without reading the canvas; alpha == 0 touches nothing.  One alpha for the
+ *   three channels.  matte: NULL, or fp32 (H,W) receiving alpha over the whole window, ring included.
+ *   HIM_E_INVALID before any launch, outputs untouched: a NULL P / m / canvas, H or W < 1, a window not inside the
+ *   canvas or without interior, feather outside 0..16384, reach outside 0..16384, dist2 or reach without feather, an
+ *   unknown profile.  Kernel layout: the 64 x 4 tile of him_canvas_paste_blend_v, lane = column.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_MEMBRANE_NO_SIDE 1
+#define HIM_MEMBRANE_MAX_N 2048
+int him_membrane_basis(int n, int lo, int hi, double* V, double* Vt, double* lam, void* stream);
+size_t him_membrane_ws(int H, int W, int sides);
+int him_membrane_solve(const float* canvas, int Hc, int Wc, int x0, int y0, int H, int W, const float* P,
+                       const double* Vy, const double* Vyt, const double* lamy, const double* Vx, const double* Vxt,
+                       const double* lamx, float* m, void* ws, int* status, void* stream);
+int him_canvas_seamless_apply(const float* P, const float* m, float* canvas, int Hc, int Wc, int x0, int y0, int H, int W,
+                              const int* dist2, int feather, int reach, int profile, float* matte, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Layout edits (the reference ships none: its public path only adds an object): take an instance out of a (label,
  * instance) canvas pair and fill the hole, and write an instance of one pair into another at another place and size.
  * Everything on `stream`, no host synchronisation, integer work, integer atomics only (add / or / min / max): results

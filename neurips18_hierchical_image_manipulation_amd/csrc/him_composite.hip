@@ -10,6 +10,9 @@
 // reads 192 contiguous bytes per tap; first / count / weights of the row are wave-uniform (scalar loads).  Tiles are
 // numbered along one grid axis (row-major), so neither window side is bound by the 65535 limit of the other axes.
 // Every canvas element is read and written by the one thread that owns it; nothing outside the window is touched.
+//
+// him_canvas_seamless_apply (include/him.h "Seamless canvas composite") writes clamp(P + m, 0, 1) -- the patch plus the
+// membrane of csrc/him_membrane.hip -- into the window's interior through the same matte (cmp_alpha) on the same tile.
 #include "him_common.h"
 
 namespace him {
@@ -97,6 +100,35 @@ __global__ void __launch_bounds__(CMP_TW* CMP_TH)
   }
 }
 
+// Seamless composite (include/him.h "Seamless canvas composite"): on the window's interior the canvas takes
+// v = clamp(P + m, 0, 1) through the matte of cmp_alpha (feather 0: alpha = 1); on the ring P + m is the photograph
+// itself, which is written as "not written".  Same tile as canvas_paste_blend_v_kernel: lane = column, a wave per row.
+__global__ void __launch_bounds__(CMP_TW* CMP_TH)
+    canvas_seamless_apply_kernel(const float* __restrict__ P, const float* __restrict__ m, float* __restrict__ canvas,
+                                 int Hc, int Wc, int x0, int y0, int H, int W, const int* __restrict__ dist2, int feather,
+                                 int reach, int profile, float* __restrict__ matte, int tiles_x) {
+  const int x = (int)(blockIdx.x % tiles_x) * CMP_TW + threadIdx.x;
+  const int y = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / tiles_x) * CMP_TH + (int)threadIdx.y);
+  if (x >= W || y >= H) return;
+  const float alpha = feather ? cmp_alpha(x, y, Hc, Wc, x0, y0, H, W, dist2, feather, reach, profile) : 1.f;
+  if (matte) matte[(long long)y * W + x] = alpha;
+  if (alpha == 0.f) return;
+  const int l = x0 > 0, r = (long long)x0 + W < Wc, t = y0 > 0, b = (long long)y0 + H < Hc;
+  if (x < l || x >= W - r || y < t || y >= H - b) return;  // the ring keeps the photograph
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const long long iw = ((long long)c * H + y) * W + x;
+    const long long i = ((long long)c * Hc + y0 + y) * Wc + x0 + x;
+    const float v = fminf(fmaxf(__fadd_rn(P[iw], m[iw]), 0.f), 1.f);
+    if (alpha == 1.f) {
+      canvas[i] = v;
+    } else {
+      const float O = canvas[i];
+      canvas[i] = __fadd_rn(O, __fmul_rn(alpha, __fsub_rn(v, O)));
+    }
+  }
+}
+
 // tiles of a (H, W) window along one grid axis; 0 when they do not fit it
 static inline long long cmp_tiles(int H, int W, int* tiles_x) {
   *tiles_x = cdiv(W, CMP_TW);
@@ -149,6 +181,31 @@ int him_canvas_paste_blend_v(const unsigned char* tmp, const int* first, const i
   hipLaunchKernelGGL(canvas_paste_blend_v_kernel, dim3((unsigned)tiles), dim3(CMP_TW, CMP_TH), 0, ST, tmp, first, count,
                      weights, ksize, canvas, Hc, Wc, x0, y0, H, W, dist2, feather, reach, profile, matte, tiles_x);
   return check_launch("canvas_paste_blend_v");
+}
+
+int him_canvas_seamless_apply(const float* P, const float* m, float* canvas, int Hc, int Wc, int x0, int y0, int H, int W,
+                              const int* dist2, int feather, int reach, int profile, float* matte, void* stream) {
+  if (!P || !m || !canvas) return fail(HIM_E_INVALID, "canvas_seamless_apply: null pointer");
+  if (H < 1 || W < 1) return fail(HIM_E_INVALID, "canvas_seamless_apply: bad shape %dx%d", W, H);
+  if (!cmp_window_inside(Hc, Wc, x0, y0, H, W))
+    return fail(HIM_E_INVALID, "canvas_seamless_apply: window (%d,%d)+(%d,%d) outside the %dx%d canvas", x0, y0, W, H, Wc,
+                Hc);
+  if (H - (y0 > 0) - ((long long)y0 + H < Hc) < 1 || W - (x0 > 0) - ((long long)x0 + W < Wc) < 1)
+    return fail(HIM_E_INVALID, "canvas_seamless_apply: a %dx%d window has no interior", W, H);
+  if (feather < 0 || feather > CMP_MAX_RADIUS)
+    return fail(HIM_E_INVALID, "canvas_seamless_apply: feather %d outside 0..%d", feather, CMP_MAX_RADIUS);
+  if (reach < 0 || reach > CMP_MAX_RADIUS)
+    return fail(HIM_E_INVALID, "canvas_seamless_apply: reach %d outside 0..%d", reach, CMP_MAX_RADIUS);
+  if (feather == 0 && (dist2 || reach != 0))
+    return fail(HIM_E_INVALID, "canvas_seamless_apply: dist2 and reach need a feather");
+  if (profile != HIM_MATTE_LINEAR && profile != HIM_MATTE_SMOOTH)
+    return fail(HIM_E_INVALID, "canvas_seamless_apply: profile %d", profile);
+  int tiles_x;
+  const long long tiles = cmp_tiles(H, W, &tiles_x);
+  if (!tiles) return fail(HIM_E_INVALID, "canvas_seamless_apply: window %dx%d too large", W, H);
+  hipLaunchKernelGGL(canvas_seamless_apply_kernel, dim3((unsigned)tiles), dim3(CMP_TW, CMP_TH), 0, ST, P, m, canvas, Hc, Wc,
+                     x0, y0, H, W, dist2, feather, reach, profile, matte, tiles_x);
+  return check_launch("canvas_seamless_apply");
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ from .. import ops
 from .._cabi import HimError
 from ..data.base_dataset import NEAREST, get_raw_transform_fn
 from ..data.device import ImageTransform
-from ..util.data_util import _blend_args, _paste_image, crop_canvas, paste_canvas
+from ..util.data_util import _blend_args, _paste_image, _paste_image_seamless, _seamless_args, crop_canvas, paste_canvas
 from ..util.util import load_script_to_opt
 
 
@@ -90,8 +90,34 @@ class JointInference(object):
                 want_matte=True)
         return img_canvas, input_dict, img_generated
 
+    def gen_image_seamless(self, bbox_sampled, img_original, label_generated, opt, *, feather=None, reach=0,
+                           profile='smooth', label_before=None):
+        """``gen_image_feathered``'s parameters with the paste done in the gradient domain (util/data_util.py
+        ``_paste_image_seamless``): the generated patch is moved onto the photograph's values along the
+        window's border before it is written.  Here ``feather=None`` means "membrane, alpha 1": the whole interior of the
+        window is replaced; with ``feather`` the matte of ``gen_image_feathered`` decides where and is left in
+        ``input_dict['matte']``.  The membrane's status ``[sides mask, ny, nx, flags]`` (device int32) is left in
+        ``input_dict['membrane']``."""
+        # refuse bad options before crop_canvas draws its random numbers
+        _seamless_args(img_original, feather, reach, profile, label_before,
+                       None if label_before is None else label_generated, False)
+        input_dict = crop_canvas(bbox_sampled, label_generated, opt, img_original=img_original, transform_img=True)
+        with torch.no_grad():
+            img_generated = self.G_mask2img.inference(input_dict['label'], torch.zeros_like(input_dict['label']),
+                                                      input_dict['image'], input_dict['mask_in'],
+                                                      input_dict['mask_out'])
+        if feather is None:
+            img_canvas = _paste_image_seamless(img_original, img_generated, input_dict, 2, profile=profile)
+        else:
+            img_canvas, input_dict['matte'] = _paste_image_seamless(
+                img_original, img_generated, input_dict, 2, feather=feather, reach=reach, profile=profile,
+                label_before=label_before, label_after=None if label_before is None else label_generated,
+                want_matte=True)
+        return img_canvas, input_dict, img_generated
+
     # -- edits of an object that is already in the scene (DESIGN.md 7r): the layout edit is ops.layout_erase /
-    # ops.layout_place, the photograph is repainted window by window with gen_image_feathered ---------------------------
+    # ops.layout_place, the photograph is repainted window by window with gen_image_feathered (``seamless``: with
+    # gen_image_seamless) -------------------------------------------------------------------------------------------------
     def _edit_classes(self, fill, things):
         n_class = int(self.opt_maskgen.label_nc)
         if fill is None:
@@ -100,13 +126,14 @@ class JointInference(object):
             fill = tuple(c for c in range(n_class) if c not in things)
         return tuple(fill), n_class
 
-    def _repaint(self, box, cls, img_canvas, label_before, label_after, opt, feather, reach, profile):
+    def _repaint(self, box, cls, img_canvas, label_before, label_after, opt, feather, reach, profile, seamless=False):
         bbox = {'bbox': [int(v) for v in box], 'cls': int(cls)}
+        gen = self.gen_image_seamless if seamless else self.gen_image_feathered
         if feather is None:
-            canvas, input_dict, _ = self.gen_image_feathered(bbox, img_canvas, label_after, opt)
+            canvas, input_dict, _ = gen(bbox, img_canvas, label_after, opt)
         else:
-            canvas, input_dict, _ = self.gen_image_feathered(bbox, img_canvas, label_after, opt, feather=feather,
-                                                             reach=reach, profile=profile, label_before=label_before)
+            canvas, input_dict, _ = gen(bbox, img_canvas, label_after, opt, feather=feather, reach=reach, profile=profile,
+                                        label_before=label_before)
         return canvas, input_dict
 
     def _erase(self, obj, label_original, inst_original, img_original, fill, things, feather, reach, profile):
@@ -123,25 +150,27 @@ class JointInference(object):
         return obj_id, box, cls, label_canvas, inst_canvas, erase
 
     def remove_object(self, obj, label_original, inst_original, img_original, opt, *, fill=None, things=None, feather=None,
-                      reach=0, profile='smooth'):
+                      reach=0, profile='smooth', seamless=False):
         """Take the object ``obj`` (an item ``(id, {'bbox', 'cls'})`` of an ``inst_info`` / ``layout_info`` dict's
         ``'objects'``, or a dict with ``id``, ``bbox``, ``cls``) out of the scene: its pixels take label and instance id of
         the nearest pixel whose class is in ``fill`` (None: every class of the layout generator's ``label_nc`` that is not
         in ``things``, by default ``ops.CITYSCAPES_THINGS``), the box table is rebuilt, and the photograph is repainted
         over the object's box with ``gen_image_feathered`` (``feather`` / ``reach`` / ``profile`` as there; with
-        ``feather`` only pixels near what the edit changed are touched).  -> ``(label_canvas, inst_canvas, img_canvas,
+        ``feather`` only pixels near what the edit changed are touched; ``seamless``: with ``gen_image_seamless``, the
+        repaint moved onto the photograph's values along the window's border).  -> ``(label_canvas, inst_canvas, img_canvas,
         info, report)``; ``report``: ``{'erase': [|R|, seeds, changed, flags], 'place': None, 'passes': [input_dict]}``.
         ``HimError`` when there is nothing to fill from: no canvas with the object still in it is returned."""
         from ..preprocess import inst_info
+        _seamless_flag(seamless)
         _, box, cls, label_canvas, inst_canvas, erase = self._erase(obj, label_original, inst_original, img_original, fill,
                                                                     things, feather, reach, profile)
         info = inst_info(inst_canvas, label_canvas)
         img_canvas, input_dict = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach,
-                                               profile)
+                                               profile, seamless)
         return label_canvas, inst_canvas, img_canvas, info, {'erase': erase, 'place': None, 'passes': [input_dict]}
 
     def move_object(self, obj, dst_box, label_original, inst_original, img_original, opt, *, fill=None, things=None,
-                    protect=(), new_id=None, feather=None, reach=0, profile='smooth'):
+                    protect=(), new_id=None, feather=None, reach=0, profile='smooth', seamless=False):
         """Move ``obj`` to ``dst_box`` (``[xmin, ymin, xmax, ymax]`` inclusive, as ``obj``'s own ``bbox``; another size
         rescales the mask as Pillow's NEAREST resize would; the box may hang over the canvas): ``remove_object``'s erase on
         the originals, then the object's original mask is written at ``dst_box`` with its class and ``new_id`` (None: its
@@ -155,6 +184,7 @@ class JointInference(object):
             raise ValueError('move_object: dst_box must be [xmin, ymin, xmax, ymax], got %r' % (dst_box,))
         if dx1 < dx0 or dy1 < dy0:
             raise ValueError('move_object: dst_box %r is empty' % (dst_box,))
+        _seamless_flag(seamless)
         obj_id, box, cls, label_e, inst_e, erase = self._erase(obj, label_original, inst_original, img_original, fill,
                                                                things, feather, reach, profile)
         label_canvas, inst_canvas, _, status = ops.layout_place(
@@ -162,18 +192,25 @@ class JointInference(object):
             cls, obj_id if new_id is None else new_id, protect=protect)
         place = [int(v) for v in status.cpu().tolist()]
         info = inst_info(inst_canvas, label_canvas)
-        img_canvas, first = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach, profile)
+        img_canvas, first = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach, profile,
+                                          seamless)
         passes = [first]
         if place[0] > 0:
             img_canvas, second = self._repaint(place[2:6], cls, img_canvas, label_original, label_canvas, opt, feather,
-                                               reach, profile)
+                                               reach, profile, seamless)
             passes.append(second)
         return label_canvas, inst_canvas, img_canvas, info, {'erase': erase, 'place': place, 'passes': passes}
 
-    def rescale_object(self, obj, scale, label_original, inst_original, img_original, opt, **kw):
+    def rescale_object(self, obj, scale, label_original, inst_original, img_original, opt, *, seamless=False, **kw):
         """``move_object`` to ``scaled_box(obj's bbox, scale)``: the box scaled about its centre."""
         _, box, _ = edit_object(obj)
-        return self.move_object(obj, scaled_box(box, scale), label_original, inst_original, img_original, opt, **kw)
+        return self.move_object(obj, scaled_box(box, scale), label_original, inst_original, img_original, opt,
+                                seamless=seamless, **kw)
+
+
+def _seamless_flag(seamless):
+    if not isinstance(seamless, bool):
+        raise ValueError('seamless must be True or False, got %r' % (seamless,))
 
 
 def edit_object(obj):

@@ -2356,6 +2356,137 @@ def canvas_paste_blend(patch, box, canvas, x0, y0, H, W, pre=0, feather=8, reach
     return canvas, matte
 
 
+# -- seamless (gradient-domain) composite: the membrane of include/him.h "Seamless canvas composite" ---------------------
+MEMBRANE_MAX_N, MEMBRANE_NO_SIDE = 2048, 1
+_MEMBRANE_BASES = {}    # (n, lo, hi, device index) -> (V, Vt, lam) fp64
+_MEMBRANE_WS = {}       # (H, W, sides, device index) -> cached workspace; one stream at a time per shape
+
+
+def membrane_sides(Hc, Wc, x0, y0, H, W, what='membrane'):
+    """(l, r, t, b, ny, nx) of an H x W window at (x0, y0) of an Hc x Wc canvas, checked on the host: a side is counted
+    when photograph lies beyond it; the interior left by the counted sides must hold a pixel and at most 2048 per axis."""
+    Hc, Wc, x0, y0, H, W = (int(v) for v in (Hc, Wc, x0, y0, H, W))
+    if H < 1 or W < 1 or x0 < 0 or y0 < 0 or x0 + W > Wc or y0 + H > Hc:
+        raise ValueError('%s: window (%d,%d)+(%d,%d) outside the %dx%d canvas' % (what, x0, y0, W, H, Wc, Hc))
+    l, r, t, b = int(x0 > 0), int(x0 + W < Wc), int(y0 > 0), int(y0 + H < Hc)
+    ny, nx = H - t - b, W - l - r
+    if ny < 1 or nx < 1:
+        raise ValueError('%s: a %dx%d window with sides l%d r%d t%d b%d has no interior' % (what, W, H, l, r, t, b))
+    if ny > MEMBRANE_MAX_N or nx > MEMBRANE_MAX_N:
+        raise ValueError('%s: interior %dx%d above %d pixels per axis' % (what, nx, ny, MEMBRANE_MAX_N))
+    return l, r, t, b, ny, nx
+
+
+def membrane_basis(n, lo, hi, device=None):
+    """``(V, Vt, lam)``: the orthonormal eigenbasis (n,n) fp64 of the 1-D second difference on ``n`` pixels with a
+    Dirichlet (1) or Neumann (0) end at ``lo`` / ``hi``, its transpose and the eigenvalues (n,), built on the device once
+    per ``(n, lo, hi, device)``.  Current stream, no host synchronisation."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MEMBRANE_MAX_N:
+        raise ValueError('membrane_basis: n must be an int in 1..%d, got %r' % (MEMBRANE_MAX_N, n))
+    if lo not in (0, 1) or hi not in (0, 1):
+        raise ValueError('membrane_basis: lo and hi are 0 or 1, got %r, %r' % (lo, hi))
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    key = (n, int(lo), int(hi), dev.index if dev.index is not None else torch.cuda.current_device())
+    got = _MEMBRANE_BASES.get(key)
+    if got is None:
+        V = torch.empty((n, n), dtype=torch.float64, device=dev)
+        Vt = torch.empty((n, n), dtype=torch.float64, device=dev)
+        lam = torch.empty((n,), dtype=torch.float64, device=dev)
+        lib.him_membrane_basis(n, int(lo), int(hi), _p(V), _p(Vt), _p(lam), _stream())
+        got = _MEMBRANE_BASES[key] = (V, Vt, lam)
+    return got
+
+
+def _membrane_P(P, what):
+    if torch.is_tensor(P) and P.dim() == 3:
+        P = P[None]
+    C, H, W = _plane_geometry(P, what)
+    if C != 3:
+        raise HimError('%s: P is (1,3,H,W), got %d channels' % (what, C))
+    return P, H, W
+
+
+def membrane_solve(canvas, x0, y0, P):
+    """``(m, status)``: the membrane (1,3,H,W) fp32 of the patch ``P`` (1,3,H,W) (what the hard paste would write) in
+    the window at ``(x0, y0)`` of the photo ``canvas`` (1,3,Hc,Wc): ``O - P`` on the window's ring, its harmonic extension
+    inside, so that ``P + m`` is the Poisson clone.  ``status``: int32 ``[sides mask, ny, nx, flags]`` on the device.
+    ValueError before any device work for a window without interior.  Current stream, no host synchronisation."""
+    P, H, W = _membrane_P(P, 'membrane_solve')
+    C, Hc, Wc = _plane_geometry(canvas, 'membrane_solve')
+    if C != 3 or P.device != canvas.device:
+        raise HimError('membrane_solve: an RGB canvas and P on one device')
+    x0, y0 = int(x0), int(y0)
+    l, r, t, b, ny, nx = membrane_sides(Hc, Wc, x0, y0, H, W, 'membrane_solve')
+    sides = l | r << 1 | t << 2 | b << 3
+    dev = canvas.device
+    m = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    if sides == 0:
+        lib.him_membrane_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), 0, 0, 0, 0, 0, 0, _p(m), 0, _p(status), _stream())
+        return m, status
+    Vy, Vyt, lamy = membrane_basis(ny, t, b, dev)
+    Vx, Vxt, lamx = membrane_basis(nx, l, r, dev)
+    key = (H, W, sides, torch.cuda.current_device())
+    ws = _MEMBRANE_WS.get(key)
+    if ws is None:
+        ws = _MEMBRANE_WS[key] = torch.empty(max(int(lib.him_membrane_ws(H, W, sides)) // 8, 1), dtype=torch.float64,
+                                             device=dev)
+    lib.him_membrane_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), _p(Vy), _p(Vyt), _p(lamy), _p(Vx), _p(Vxt), _p(lamx),
+                           _p(m), _p(ws), _p(status), _stream())
+    return m, status
+
+
+def canvas_seamless_apply(P, m, canvas, x0, y0, *, feather=None, reach=0, dist2=None, profile='smooth', want_matte=False):
+    """In place -> ``(canvas, matte or None)``: the window's interior takes ``clamp(P + m, 0, 1)`` through the matte of
+    ``canvas_paste_blend`` (``feather=None``: alpha 1); the ring keeps the photograph."""
+    P, H, W = _membrane_P(P, 'canvas_seamless_apply')
+    _, Hc, Wc = _plane_geometry(canvas, 'canvas_seamless_apply')
+    _chk(m)
+    if tuple(m.shape) != tuple(P.shape) or m.device != canvas.device or P.device != canvas.device:
+        raise HimError('canvas_seamless_apply: P and m are (1,3,H,W) on the canvas device')
+    membrane_sides(Hc, Wc, x0, y0, H, W, 'canvas_seamless_apply')
+    if feather is None:
+        if reach != 0 or dist2 is not None:
+            raise ValueError('canvas_seamless_apply: reach / dist2 need feather')
+        fe, re_, prof = 0, 0, MATTE_PROFILES.get(profile, 1)
+    else:
+        fe, re_, prof = matte_args(feather, reach, profile, 'canvas_seamless_apply')
+    if dist2 is not None:
+        if not torch.is_tensor(dist2) or not dist2.is_cuda or dist2.dtype != torch.int32 or dist2.device != canvas.device \
+                or tuple(dist2.shape) not in ((H, W), (1, H, W)):
+            raise HimError('canvas_seamless_apply: dist2 must be an int32 (%d,%d) tensor on the canvas device' % (H, W))
+        dist2 = dist2.contiguous()
+    matte = torch.empty((1, 1, H, W), dtype=torch.float32, device=canvas.device) if want_matte else None
+    lib.him_canvas_seamless_apply(_p(P), _p(m), _p(canvas), Hc, Wc, int(x0), int(y0), H, W, _p(dist2), fe, re_, prof,
+                                  _p(matte), _stream())
+    return canvas, matte
+
+
+def canvas_paste_seamless(cropped, box, canvas, x0, y0, H, W, pre, *, feather=None, reach=0, dist2=None, profile='smooth',
+                          want_matte=False):
+    """``canvas_paste_bicubic`` in the gradient domain, in place -> ``(canvas, matte or None, status)``.  P, what the hard
+    paste would write, comes from the same horizontal pass and ``him_canvas_paste_bicubic_v`` run into an (H,W) scratch
+    canvas; the membrane of ``membrane_solve`` moves it onto the photograph's values along the window's border, and
+    ``clamp(P + m, 0, 1)`` enters the window's interior through the matte of ``canvas_paste_blend`` (``feather=None``:
+    alpha 1 on the interior).  Options are checked on the host before any device work.  Current stream, no host
+    synchronisation."""
+    H, W = int(H), int(W)
+    membrane_sides(canvas.shape[-2], canvas.shape[-1], x0, y0, H, W, 'canvas_paste_seamless')
+    if feather is None:
+        if reach != 0 or dist2 is not None:
+            raise ValueError('canvas_paste_seamless: reach / dist2 need feather')
+        if profile not in MATTE_PROFILES:
+            raise ValueError('canvas_paste_seamless: profile %r (one of %s)' % (profile, ', '.join(MATTE_PROFILES)))
+    else:
+        matte_args(feather, reach, profile, 'canvas_paste_seamless')
+    scratch = torch.empty((1, 3, H, W), dtype=torch.float32, device=canvas.device)
+    _bicubic(cropped, box, H, W, pre, scratch, (0, 0), False)
+    m, status = membrane_solve(canvas, x0, y0, scratch)
+    _, matte = canvas_seamless_apply(scratch, m, canvas, x0, y0, feather=feather, reach=reach, dist2=dist2, profile=profile,
+                                     want_matte=want_matte)
+    return canvas, matte, status
+
+
 def canvas_paste_window(src, canvas, x0, y0):
     """In place: canvas[0, :, y0:y0+h, x0:x0+w] = src (1,C,h,w) fp32 or int64 (as fp32)."""
     src = src.contiguous()

@@ -109,17 +109,8 @@ def _blend_args(original, feather, reach, profile, label_before, label_after, wa
     return feather, reach, profile
 
 
-def _paste_image(original, cropped, info_dict, pre, *, feather=None, reach=0, profile='smooth', label_before=None,
-                 label_after=None, want_matte=False):
-    """The is_img branch: the ``output_bbox`` slice of ``cropped`` (1,3,fs,fs), ToPILImage of pre(v), BICUBIC to the
-    global window, ToTensor, written into a clone of ``original``.
-
-    ``feather`` (pixels, None: the hard rectangle above, unchanged) writes through a matte instead (DESIGN.md 7p): it
-    fades over ``feather`` pixels towards every side of the window with photograph behind it and, given the label canvas
-    before and after the layout edit, from full strength within ``reach`` pixels of the pixels the edit changed to nothing
-    at ``reach + feather`` (``canvas_changed`` -> ``distance_transform`` -> the blended paste); ``profile`` 'linear' or
-    'smooth'.  ``want_matte``: -> (canvas, matte (1,1,H,W))."""
-    blend = _blend_args(original, feather, reach, profile, label_before, label_after, want_matte)
+def _paste_windows(original, cropped, info_dict):
+    """``_paste_image``'s window arithmetic -> (x1, y1, width, height) on the canvas and (x3, y3, sw, sh) in the patch."""
     x1, y1, x2, y2 = _window(info_dict['output_bbox_global'])
     width, height = x2 - x1 + 1, y2 - y1 + 1
     x3, y3, x4, y4 = (int(v) for v in info_dict['output_bbox'].int())
@@ -131,6 +122,29 @@ def _paste_image(original, cropped, info_dict, pre, *, feather=None, reach=0, pr
             (height, width):
         raise ValueError('paste_canvas: a %dx%d patch window does not fit the %dx%d canvas window at (%d,%d)'
                          % (sw, sh, width, height, x1, y1))
+    return (x1, y1, width, height), (x3, y3, sw, sh)
+
+
+def _seamless_args(original, feather, reach, profile, label_before, label_after, want_matte):
+    """The seamless paste's options, checked on the host before any device work: ``_blend_args``, and without ``feather``
+    (membrane, alpha 1) the profile still has to be a known one."""
+    if feather is None and profile not in ops.MATTE_PROFILES:
+        raise ValueError('paste_canvas: profile %r (one of %s)' % (profile, ', '.join(ops.MATTE_PROFILES)))
+    return _blend_args(original, feather, reach, profile, label_before, label_after, want_matte)
+
+
+def _paste_image(original, cropped, info_dict, pre, *, feather=None, reach=0, profile='smooth', label_before=None,
+                 label_after=None, want_matte=False):
+    """The is_img branch: the ``output_bbox`` slice of ``cropped`` (1,3,fs,fs), ToPILImage of pre(v), BICUBIC to the
+    global window, ToTensor, written into a clone of ``original``.
+
+    ``feather`` (pixels, None: the hard rectangle above, unchanged) writes through a matte instead (DESIGN.md 7p): it
+    fades over ``feather`` pixels towards every side of the window with photograph behind it and, given the label canvas
+    before and after the layout edit, from full strength within ``reach`` pixels of the pixels the edit changed to nothing
+    at ``reach + feather`` (``canvas_changed`` -> ``distance_transform`` -> the blended paste); ``profile`` 'linear' or
+    'smooth'.  ``want_matte``: -> (canvas, matte (1,1,H,W))."""
+    blend = _blend_args(original, feather, reach, profile, label_before, label_after, want_matte)
+    (x1, y1, width, height), (x3, y3, sw, sh) = _paste_windows(original, cropped, info_dict)
     raw = original.clone()
     if blend is None:
         ops.canvas_paste_bicubic(cropped.contiguous(), (x3, y3, x3 + sw, y3 + sh), raw, x1, y1, height, width, pre)
@@ -158,6 +172,40 @@ def paste_canvas_feathered(original, cropped, info_dict, method=BICUBIC, resize=
         raise NotImplementedError('paste_canvas(is_img=True): only Image.BICUBIC is on the HIP path')
     return _paste_image(original, cropped, info_dict, 0, feather=feather, reach=reach, profile=profile,
                         label_before=label_before, label_after=label_after, want_matte=want_matte)
+
+
+def _paste_image_seamless(original, cropped, info_dict, pre, *, feather=None, reach=0, profile='smooth', label_before=None,
+                          label_after=None, want_matte=False):
+    """``_paste_image`` in the gradient domain: the patch is moved onto the photograph's values along the
+    window's border by the membrane of ``ops.membrane_solve`` before it is written, so no offset in exposure or colour
+    between generator and photograph survives.  ``feather=None``: the whole interior of the window is replaced (alpha 1);
+    otherwise the matte of ``_paste_image`` decides where.  The membrane's status is left in ``info_dict['membrane']``."""
+    _seamless_args(original, feather, reach, profile, label_before, label_after, want_matte)
+    (x1, y1, width, height), (x3, y3, sw, sh) = _paste_windows(original, cropped, info_dict)
+    ops.membrane_sides(original.shape[2], original.shape[3], x1, y1, height, width, 'paste_canvas_seamless')
+    raw = original.clone()
+    dist2 = None
+    if label_before is not None:
+        changed = ops.canvas_changed(label_before.contiguous(), label_after.contiguous(), x1, y1, height, width)
+        dist2 = ops.distance_transform(changed, rule='nonzero')[0]
+    _, matte, info_dict['membrane'] = ops.canvas_paste_seamless(
+        cropped.contiguous(), (x3, y3, x3 + sw, y3 + sh), raw, x1, y1, height, width, pre, feather=feather, reach=reach,
+        dist2=dist2, profile=profile, want_matte=want_matte)
+    return (raw, matte) if want_matte else raw
+
+
+def paste_canvas_seamless(original, cropped, info_dict, method=BICUBIC, resize=True, is_img=True, *, feather=None,
+                          reach=0, profile='smooth', label_before=None, label_after=None, want_matte=False):
+    """``paste_canvas_feathered``'s parameters, the image paste done in the gradient domain (see
+    ``_paste_image_seamless``).  Here ``feather=None`` means "membrane, alpha 1".  A label paste (``is_img`` False) has no
+    gradient domain: ValueError."""
+    if not is_img:
+        raise ValueError('paste_canvas_seamless: an image paste; a label map (is_img=False) is copied by paste_canvas')
+    _seamless_args(original, feather, reach, profile, label_before, label_after, want_matte)
+    if method != BICUBIC:
+        raise NotImplementedError('paste_canvas(is_img=True): only Image.BICUBIC is on the HIP path')
+    return _paste_image_seamless(original, cropped, info_dict, 0, feather=feather, reach=reach, profile=profile,
+                                 label_before=label_before, label_after=label_after, want_matte=want_matte)
 
 
 def paste_canvas(original, cropped, info_dict, method=NEAREST, resize=True, is_img=False):
