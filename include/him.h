@@ -1111,6 +1111,70 @@ int him_canvas_seamless_apply(const float* P, const float* m, float* canvas, int
                               const int* dist2, int feather, int reach, int profile, float* matte, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Region Poisson clone (the reference ships none): Poisson image editing of a patch into the photograph on an
+ * ARBITRARY pixel set of the paste window, the photograph being Dirichlet data all around the set -- what keeps a moved
+ * object's own pixels.  Everything on `stream`, no host synchronisation, no host read between launches, no atomics on
+ * floating-point data, all vectors and scalars fp64, results bit-identical from run to run.
+ *
+ * Inputs: the photo canvas O (3,Hc,Wc) fp32, a window H x W at (x0, y0) inside it, the patch P (3,H,W) fp32 (what a hard
+ *   paste would write on the window), a region plane (H,W) uint8 (nonzero: clone this pixel), mixed in {0,1}.
+ * Sides and ring: as in "Seamless canvas composite" (left counted iff x0 > 0, ...; sides mask l | r << 1 | t << 2 |
+ *   b << 3; ring = the window's first / last row / column on each counted side).
+ * Unknown set Omega = {region != 0} minus the ring.  N(p): the 4-neighbours of p inside the window (none beyond an
+ *   uncounted side: Neumann), deg(p) = |N(p)| in 2..4.  Per channel, for p in Omega, with f~(q) = f(q) for q in Omega and
+ *   O(q) otherwise:
+ *       deg(p) f(p) - sum_{q in N(p)} f~(q) = sum_{q in N(p)} v_pq
+ *   mixed 0: v_pq = P(p) - P(q).   mixed 1: v_pq = O(p) - O(q) when |O(p) - O(q)| > |P(p) - P(q)| (strictly: ties take
+ *   the patch), else P(p) - P(q).  All differences in fp64 from the fp32 values.
+ *   The solver works on the correction u = f - P (0 outside Omega):
+ *       deg(p) u(p) - sum_{q in N(p) in Omega} u(q) = sum_{q in N(p) not in Omega} (O(q) - P(q))
+ *                                                     [+ sum_{q in N(p)} (v_pq - (P(p) - P(q))) when mixed]
+ *   The system is symmetric positive definite unless Omega is the whole window and no side is counted
+ *   (HIM_REGION_POISSON_SINGULAR: u := 0).  The dense float64 solve of these equations is the authority.
+ *
+ * him_region_poisson_ws: bytes of workspace for an H x W window; 0 for H or W outside 1..2048.
+ * him_region_poisson_solve: conjugate gradients, no preconditioner, the three channels in lockstep with their own
+ *   scalars.  A channel stops when r.r <= rtol^2 b.b and is frozen: none of its vectors is touched again.  b.b == 0: u = 0,
+ *   0 iterations, resid 0, no division is reached; p.Ap <= 0 stops the channel the same way.  At most max_iter
+ *   iterations (the callers' default is 6 (H + W): CG on the full L x L window, the worst region a window admits, has
+ *   sqrt(kappa) ~ 0.64 L and reaches 1e-10 in about 7.6 L iterations, the cap there is 12 L; a cap, not a measurement).
+ *   u      (3,H,W) fp64: the correction, exactly 0 outside Omega.
+ *   resid  fp64[3]: the recursive ||r||_2 / ||b||_2 of each channel at its stop (0 where b.b == 0 or a flag of bits 0, 1, 3
+ *          is set).
+ *   status int32[8]: [sides mask, |Omega|, region pixels dropped on the ring, iterations run (maximum over channels),
+ *          flags, 0, 0, 0].  Flags: HIM_REGION_POISSON_EMPTY (Omega is empty, nothing solved), _SINGULAR (above),
+ *          _MAX_ITER_HIT (a channel ended above rtol), _NONFINITE (a non-finite value of P or O was read on Omega or on
+ *          its neighbours: u := 0).
+ *   ws     him_region_poisson_ws bytes, 8-byte aligned; every slot that is read is written by the call first.
+ *   HIM_E_INVALID before any launch, outputs untouched: a NULL canvas / P / region / u / status / resid, a window not
+ *   inside the canvas, H or W < 1 or > 2048, rtol outside (0, 1) or NaN, max_iter < 1 or > 2^20 (the call enqueues
+ *   2 max_iter + 2 launches), mixed outside {0,1}, u, resid or ws not aligned to 8 bytes.  HIM_E_WORKSPACE: ws NULL or
+ *   ws_bytes too small.
+ *   Kernel layout: 256-thread workgroups own 64 x 4 tiles (lane = column, the three channels in one thread), at most
+ *   1024 workgroups taking the tiles in strides.  init (deg plane, b, u := 0, partial b.b and counts) -> per iteration
+ *   dir (the sum of the r.r partials, the stop decision and beta in every workgroup, p = r + beta p_old evaluated at the
+ *   pixel and its neighbours from the other of two direction buffers, A p, partial p.Ap) and upd (the sum of the p.Ap
+ *   partials, alpha, u += alpha p, r -= alpha A p, partial r.r) -> finish (status, resid).  Iteration boundaries are
+ *   kernel boundaries; once every channel has stopped a launch returns after loading three ints.
+ * him_region_poisson_apply: canvas[p] = min(max((float)(P(p) + u(p)), 0), 1) for p in Omega: the sum of the fp32 patch
+ *   value and the fp64 correction is narrowed to fp32 once, its only fp32 rounding; every other canvas element is neither
+ *   read nor written.  HIM_E_INVALID: a NULL pointer, a window not inside the canvas, H or W
+ *   outside 1..2048, u not aligned to 8 bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_REGION_POISSON_EMPTY 1
+#define HIM_REGION_POISSON_SINGULAR 2
+#define HIM_REGION_POISSON_MAX_ITER_HIT 4
+#define HIM_REGION_POISSON_NONFINITE 8
+#define HIM_REGION_POISSON_MAX_N 2048
+#define HIM_REGION_POISSON_MAX_ITER 1048576
+size_t him_region_poisson_ws(int H, int W);
+int him_region_poisson_solve(const float* canvas, int Hc, int Wc, int x0, int y0, int H, int W, const float* P,
+                             const unsigned char* region, int mixed, double rtol, int max_iter, double* u, int* status,
+                             double* resid, void* ws, size_t ws_bytes, void* stream);
+int him_region_poisson_apply(const float* P, const double* u, const unsigned char* region, float* canvas, int Hc, int Wc,
+                             int x0, int y0, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Layout edits (the reference ships none: its public path only adds an object): take an instance out of a (label,
  * instance) canvas pair and fill the hole, and write an instance of one pair into another at another place and size.
  * Everything on `stream`, no host synchronisation, integer work, integer atomics only (add / or / min / max): results

@@ -171,6 +171,10 @@ _SIGS = {
     'him_membrane_solve': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P]),
     'him_canvas_seamless_apply': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P,
                                           P]),
+    'him_region_poisson_ws': (c_size_t, [c_int, c_int]),
+    'him_region_poisson_solve': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_double, c_int, P, P, P,
+                                         P, c_size_t, P]),
+    'him_region_poisson_apply': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'him_layout_erase_workspace': (c_size_t, [c_int, c_int]),
     'him_layout_erase': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P, P, P, c_size_t, P]),
     'him_layout_place': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P] +

@@ -170,13 +170,20 @@ class JointInference(object):
         return label_canvas, inst_canvas, img_canvas, info, {'erase': erase, 'place': None, 'passes': [input_dict]}
 
     def move_object(self, obj, dst_box, label_original, inst_original, img_original, opt, *, fill=None, things=None,
-                    protect=(), new_id=None, feather=None, reach=0, profile='smooth', seamless=False):
+                    protect=(), new_id=None, feather=None, reach=0, profile='smooth', seamless=False,
+                    keep_appearance=False, mixed=False):
         """Move ``obj`` to ``dst_box`` (``[xmin, ymin, xmax, ymax]`` inclusive, as ``obj``'s own ``bbox``; another size
         rescales the mask as Pillow's NEAREST resize would; the box may hang over the canvas): ``remove_object``'s erase on
         the originals, then the object's original mask is written at ``dst_box`` with its class and ``new_id`` (None: its
         own id), behind the pixels whose class is in ``protect``.  The photograph is repainted over the vacated box and
         then, on that result, over the box of the pixels written.  -> as ``remove_object``; ``report['place']``:
-        ``[written, blocked, xmin, ymin, xmax, ymax]``, ``report['passes']`` one ``input_dict`` per repaint."""
+        ``[written, blocked, xmin, ymin, xmax, ymax]``, ``report['passes']`` one ``input_dict`` per repaint.
+
+        ``keep_appearance``: the second pass is not a repaint: the object's own pixels, cut from the untouched original
+        photograph at its box and resized to ``dst_box`` as Pillow's BICUBIC resize would, are Poisson-cloned onto the
+        pixels ``layout_place`` wrote, the canvas after the first repaint being the boundary data
+        (``ops.canvas_clone_region``; ``mixed``: per neighbour pair the stronger of the two gradients).  The
+        pass's entry of ``report['passes']`` is then ``{'clone': status as host ints, 'resid': [...]}``."""
         from ..preprocess import inst_info
         try:
             dx0, dy0, dx1, dy1 = (int(v) for v in dst_box)
@@ -185,9 +192,10 @@ class JointInference(object):
         if dx1 < dx0 or dy1 < dy0:
             raise ValueError('move_object: dst_box %r is empty' % (dst_box,))
         _seamless_flag(seamless)
+        _clone_flags(keep_appearance, mixed)
         obj_id, box, cls, label_e, inst_e, erase = self._erase(obj, label_original, inst_original, img_original, fill,
                                                                things, feather, reach, profile)
-        label_canvas, inst_canvas, _, status = ops.layout_place(
+        label_canvas, inst_canvas, placed, status = ops.layout_place(
             label_e, inst_e, inst_original, obj_id, (box[0], box[1], box[2] + 1, box[3] + 1), (dx0, dy0, dx1 + 1, dy1 + 1),
             cls, obj_id if new_id is None else new_id, protect=protect)
         place = [int(v) for v in status.cpu().tolist()]
@@ -195,7 +203,12 @@ class JointInference(object):
         img_canvas, first = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach, profile,
                                           seamless)
         passes = [first]
-        if place[0] > 0:
+        if place[0] > 0 and keep_appearance:
+            img_canvas, clone, resid = ops.canvas_clone_region(
+                img_original, (box[0], box[1], box[2] + 1, box[3] + 1), img_canvas, (dx0, dy0, dx1 + 1, dy1 + 1), placed,
+                mixed=mixed)
+            passes.append({'clone': [int(v) for v in clone.cpu().tolist()], 'resid': [float(v) for v in resid.cpu().tolist()]})
+        elif place[0] > 0:
             img_canvas, second = self._repaint(place[2:6], cls, img_canvas, label_original, label_canvas, opt, feather,
                                                reach, profile, seamless)
             passes.append(second)
@@ -206,6 +219,14 @@ class JointInference(object):
         _, box, _ = edit_object(obj)
         return self.move_object(obj, scaled_box(box, scale), label_original, inst_original, img_original, opt,
                                 seamless=seamless, **kw)
+
+
+def _clone_flags(keep_appearance, mixed):
+    for name, v in (('keep_appearance', keep_appearance), ('mixed', mixed)):
+        if not isinstance(v, bool):
+            raise ValueError('%s must be True or False, got %r' % (name, v))
+    if mixed and not keep_appearance:
+        raise ValueError('mixed=True needs keep_appearance=True')
 
 
 def _seamless_flag(seamless):

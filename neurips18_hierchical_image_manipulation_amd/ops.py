@@ -2487,6 +2487,130 @@ def canvas_paste_seamless(cropped, box, canvas, x0, y0, H, W, pre, *, feather=No
     return canvas, matte, status
 
 
+# -- region Poisson clone: include/him.h "Region Poisson clone" -----------------------------------------------------------
+REGION_POISSON_MAX_N, REGION_POISSON_MAX_ITER = 2048, 1 << 20
+REGION_POISSON_EMPTY, REGION_POISSON_SINGULAR, REGION_POISSON_MAX_ITER_HIT, REGION_POISSON_NONFINITE = 1, 2, 4, 8
+_REGION_POISSON_WS = {}  # (H, W, device index) -> cached workspace; one stream at a time per shape
+
+
+def region_poisson_args(H, W, mixed, rtol, max_iter, what='region_poisson'):
+    """(mixed 0/1, rtol, max_iter) of a region clone on an H x W window, checked on the host: ``mixed`` a bool, ``rtol``
+    a float in (0, 1), ``max_iter`` None (the cap 6 (H + W)) or an int in 1..2^20."""
+    H, W = int(H), int(W)
+    if not 1 <= H <= REGION_POISSON_MAX_N or not 1 <= W <= REGION_POISSON_MAX_N:
+        raise ValueError('%s: window %dx%d outside 1..%d per axis' % (what, W, H, REGION_POISSON_MAX_N))
+    if not isinstance(mixed, bool):
+        raise ValueError('%s: mixed must be True or False, got %r' % (what, mixed))
+    if isinstance(rtol, bool) or not isinstance(rtol, (int, float)) or not 0.0 < float(rtol) < 1.0:
+        raise ValueError('%s: rtol must be a number in (0, 1), got %r' % (what, rtol))
+    if max_iter is None:
+        max_iter = 6 * (H + W)
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 1 <= max_iter <= REGION_POISSON_MAX_ITER:
+        raise ValueError('%s: max_iter must be None or an int in 1..%d, got %r' % (what, REGION_POISSON_MAX_ITER, max_iter))
+    return int(mixed), float(rtol), max_iter
+
+
+def _region_inside(canvas, x0, y0, H, W, what):
+    Hc, Wc, x0, y0 = int(canvas.shape[-2]), int(canvas.shape[-1]), int(x0), int(y0)
+    if x0 < 0 or y0 < 0 or x0 + W > Wc or y0 + H > Hc:
+        raise ValueError('%s: window (%d,%d)+(%d,%d) outside the %dx%d canvas' % (what, x0, y0, W, H, Wc, Hc))
+
+
+def _region_window(canvas, x0, y0, H, W, what):
+    C, Hc, Wc = _plane_geometry(canvas, what)
+    if C != 3:
+        raise HimError('%s: an RGB canvas, got %d channels' % (what, C))
+    return Hc, Wc, int(x0), int(y0)
+
+
+def _region_plane(region, H, W, device, what):
+    if not torch.is_tensor(region) or not region.is_cuda or region.dtype != torch.uint8 or region.device != device \
+            or tuple(region.shape) not in ((H, W), (1, H, W)):
+        raise HimError('%s: region must be a uint8 (%d,%d) tensor on the canvas device' % (what, H, W))
+    return region.contiguous()
+
+
+def region_poisson_solve(canvas, x0, y0, P, region, *, mixed=False, rtol=1e-7, max_iter=None):
+    """``(u, status, resid)``: the correction ``u`` (1,3,H,W) fp64 that makes ``P + u`` the Poisson clone of the patch
+    ``P`` (1,3,H,W) into the photo ``canvas`` (1,3,Hc,Wc) on the pixels of ``region`` (uint8 (H,W), nonzero = clone) of the
+    window at ``(x0, y0)``, the photograph being Dirichlet data all around them; ``mixed``: per neighbour pair the stronger
+    of the patch's and the photograph's gradient.  Conjugate gradients to ``rtol`` (relative residual), at most
+    ``max_iter`` iterations (None: 6 (H + W)).  ``status``: int32 ``[sides mask, |Omega|, region pixels dropped on the
+    ring, iterations, flags, 0, 0, 0]``, ``resid``: fp64 (3,), both on the device.  Options are checked on the host before
+    any device work.  Current stream, no host synchronisation."""
+    what = 'region_poisson_solve'
+    mixed, rtol, max_iter = region_poisson_args(P.shape[-2], P.shape[-1], mixed, rtol, max_iter, what)
+    _region_inside(canvas, x0, y0, P.shape[-2], P.shape[-1], what)
+    P, H, W = _membrane_P(P, what)
+    Hc, Wc, x0, y0 = _region_window(canvas, x0, y0, H, W, what)
+    if P.device != canvas.device:
+        raise HimError('%s: canvas and P on one device' % what)
+    dev = canvas.device
+    region = _region_plane(region, H, W, dev, what)
+    with torch.cuda.device(dev):
+        u = torch.empty((1, 3, H, W), dtype=torch.float64, device=dev)
+        status = torch.empty(8, dtype=torch.int32, device=dev)
+        resid = torch.empty(3, dtype=torch.float64, device=dev)
+        key = (H, W, dev.index)
+        ws = _REGION_POISSON_WS.get(key)
+        if ws is None:
+            ws = _REGION_POISSON_WS[key] = torch.empty(int(lib.him_region_poisson_ws(H, W)) // 8, dtype=torch.float64,
+                                                       device=dev)
+        lib.him_region_poisson_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), _p(region), mixed, rtol, max_iter, _p(u),
+                                     _p(status), _p(resid), _p(ws), ws.numel() * 8, _stream())
+    return u, status, resid
+
+
+def region_poisson_apply(P, u, region, canvas, x0, y0):
+    """In place -> ``canvas``: ``clamp(P + u, 0, 1)`` (one fp32 add) on the region's pixels off the ring; nothing else of
+    the canvas is read or written."""
+    what = 'region_poisson_apply'
+    region_poisson_args(P.shape[-2], P.shape[-1], False, 0.5, None, what)
+    _region_inside(canvas, x0, y0, P.shape[-2], P.shape[-1], what)
+    P, H, W = _membrane_P(P, what)
+    Hc, Wc, x0, y0 = _region_window(canvas, x0, y0, H, W, what)
+    if not torch.is_tensor(u) or not u.is_cuda or u.dtype != torch.float64 or u.device != canvas.device \
+            or P.device != canvas.device or tuple(u.shape) not in ((3, H, W), (1, 3, H, W)):
+        raise HimError('%s: u is fp64 (1,3,%d,%d) and P fp32 on the canvas device' % (what, H, W))
+    region = _region_plane(region, H, W, canvas.device, what)
+    with torch.cuda.device(canvas.device):
+        lib.him_region_poisson_apply(_p(P), _p(u.contiguous()), _p(region), _p(canvas), Hc, Wc, x0, y0, H, W, _stream())
+    return canvas
+
+
+def canvas_clone_region(src, src_box, canvas, dst_box, region, *, mixed=False, rtol=1e-7, max_iter=None):
+    """Clone the pixels of ``src`` (1,3,Hs,Ws) inside ``src_box`` into ``canvas`` (1,3,Hc,Wc) at ``dst_box`` (both
+    ``[xmin, ymin, xmax, ymax)``, as ``layout_place`` takes them), in place -> ``(canvas, status, resid)``.  P is
+    ``canvas_crop_bicubic(src, src_box, dh, dw, normalize=False)`` -- Pillow's resize of the source box to the
+    destination's size -- cut to the part of ``dst_box`` inside the canvas; that part is the window.  ``region``: a
+    canvas-sized uint8 (Hc,Wc) plane (``layout_place``'s ``changed``), read on the window.  ``src`` must not alias
+    ``canvas``.  ``region_poisson_solve`` then ``region_poisson_apply``; options are checked on the host before any device
+    work.  Current stream, no host synchronisation."""
+    what = 'canvas_clone_region'
+    sx0, sy0, sx1, sy1 = _layout_box(src_box, what + ': src_box')
+    dx0, dy0, dx1, dy1 = _layout_box(dst_box, what + ': dst_box')
+    Hc, Wc, Hs, Ws = (int(v) for v in (canvas.shape[-2], canvas.shape[-1], src.shape[-2], src.shape[-1]))
+    if sx0 < 0 or sy0 < 0 or sx1 > Ws or sy1 > Hs:
+        raise ValueError('%s: src_box [%d, %d, %d, %d) is not inside the %d x %d source' % (what, sx0, sy0, sx1, sy1, Ws, Hs))
+    cx0, cy0, cx1, cy1 = max(dx0, 0), max(dy0, 0), min(dx1, Wc), min(dy1, Hc)
+    if cx1 <= cx0 or cy1 <= cy0:
+        raise ValueError('%s: dst_box [%d, %d, %d, %d) does not meet the %d x %d canvas' % (what, dx0, dy0, dx1, dy1, Wc, Hc))
+    H, W = cy1 - cy0, cx1 - cx0
+    region_poisson_args(H, W, mixed, rtol, max_iter, what)
+    if src.data_ptr() == canvas.data_ptr() or src.device != canvas.device:
+        raise ValueError('%s: src and canvas are two tensors on one device' % what)
+    _plane_geometry(canvas, what)
+    if not torch.is_tensor(region) or not region.is_cuda or region.dtype != torch.uint8 or region.device != canvas.device \
+            or tuple(region.shape) not in ((Hc, Wc), (1, Hc, Wc)):
+        raise HimError('%s: region must be a uint8 (%d,%d) tensor on the canvas device' % (what, Hc, Wc))
+    P = canvas_crop_bicubic(src, (sx0, sy0, sx1, sy1), dy1 - dy0, dx1 - dx0, normalize=False)
+    P = P[:, :, cy0 - dy0:cy1 - dy0, cx0 - dx0:cx1 - dx0].contiguous()
+    window = region.reshape(Hc, Wc)[cy0:cy1, cx0:cx1].contiguous()
+    u, status, resid = region_poisson_solve(canvas, cx0, cy0, P, window, mixed=mixed, rtol=rtol, max_iter=max_iter)
+    region_poisson_apply(P, u, window, canvas, cx0, cy0)
+    return canvas, status, resid
+
+
 def canvas_paste_window(src, canvas, x0, y0):
     """In place: canvas[0, :, y0:y0+h, x0:x0+w] = src (1,C,h,w) fp32 or int64 (as fp32)."""
     src = src.contiguous()
