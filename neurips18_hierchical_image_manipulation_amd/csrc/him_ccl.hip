@@ -249,11 +249,8 @@ __global__ __launch_bounds__(256) void ccl_count_kernel(const int* __restrict__ 
     int n = 0;
 #pragma unroll
     for (int k = 0; k < CCL_PER; ++k) n += ccl_kept(parent, area, pb, l0 + k * 256 + threadIdx.x, HW, min_area);
-    n = wave_sum_i32(n);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) bcount[c] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    n = block_sum_i32(n, sh);
+    if (threadIdx.x == 0) bcount[c] = n;
   }
 }
 

@@ -71,7 +71,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
 
 // ---- the double and int sums the bit-identical-from-run-to-run claims of the metric / guard / augment kernels rest on.
 // Distinct names, not overloads of wave_sum: a call with an implicit conversion must not change what it resolves to.
-// All three return the SAME value in EVERY thread (of the wave / of the workgroup): the xor butterfly adds the same two
+// All of them return the SAME value in EVERY thread (of the wave / of the workgroup): the xor butterfly adds the same two
 // operands in both partners (a + b is commutative), and the sum over the four waves is one fixed expression.
 // (bias_grad1_kernel in him_conv_wgrad.inc keeps its own double butterfly: it has no leading barrier, so it is not
 // block_sum_f64.)
@@ -89,6 +89,14 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 // 256-thread workgroups.  `sh` holds 4 doubles; the leading barrier makes back-to-back calls on one `sh` safe.
 __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// the same for ints; `sh` holds 4 ints
+__device__ __forceinline__ int block_sum_i32(int v, int* sh) {
+  v = wave_sum_i32(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();

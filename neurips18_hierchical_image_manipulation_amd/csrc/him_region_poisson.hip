@@ -78,14 +78,6 @@ __host__ __device__ inline long long rp_ws_bytes(int H, int W) {
   return rp_off_planes() + 4LL * 3 * n * 8 + (n + 7) / 8 * 8;
 }
 
-__device__ __forceinline__ int rp_block_sum_i32(int v, int* shi) {
-  v = wave_sum_i32(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (shi[0] + shi[1]) + (shi[2] + shi[3]);
-}
-
 __device__ __forceinline__ int rp_load_done(const RpState* st, int c) {
   return __hip_atomic_load(&st->done_at[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -177,7 +169,7 @@ __global__ void __launch_bounds__(256)
   const int counts[3] = {n_omega, n_ring, n_bad};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int s = rp_block_sum_i32(counts[c], shi);
+    const int s = block_sum_i32(counts[c], shi);
     if (threadIdx.x == 0) ipart[c * RP_MAX_BLOCKS + blockIdx.x] = s;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -206,7 +198,7 @@ __device__ __forceinline__ void rp_head(const RpGeom& g, int k, double rtol2, co
     for (int c = 0; c < 3; ++c) {
       int s = 0;
       for (int i = threadIdx.x; i < g.nblk; i += 256) s += ipart[c * RP_MAX_BLOCKS + i];
-      cnt[c] = rp_block_sum_i32(s, shi);
+      cnt[c] = block_sum_i32(s, shi);
     }
     h->n_omega = cnt[0], h->n_ring = cnt[1], h->n_bad = cnt[2];
     h->flags = 0;

@@ -180,14 +180,8 @@ __global__ __launch_bounds__(256) void swd_gather_kernel(const float* __restrict
       const double rn = swd_block_reduce<1>(mn[c], sh), rx = swd_block_reduce<2>(mx[c], sh);
       if (tid == 0) slot[c * SWD_NSTAT] = rs, slot[c * SWD_NSTAT + 1] = rq, slot[c * SWD_NSTAT + 2] = rn, slot[c * SWD_NSTAT + 3] = rx;
     }
-    clamped = wave_sum_i32(clamped);
-    __syncthreads();
-    if ((tid & 63) == 0) shc[tid >> 6] = clamped;
-    __syncthreads();
-    if (tid == 0) {
-      const int n = (shc[0] + shc[1]) + (shc[2] + shc[3]);
-      if (n) atomicAdd(status, n);
-    }
+    const int n = block_sum_i32(clamped, shc);
+    if (tid == 0 && n) atomicAdd(status, n);
   }
 }
 

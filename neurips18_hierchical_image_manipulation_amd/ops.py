@@ -51,66 +51,52 @@ def _direct(p):
     return getattr(p, '_him_direct_grad', False) and p.grad is not None
 
 
+from .config import SCHED
+
+_STREAMS = {}           # (name, device) -> torch.cuda.Stream, created on first use
+
+
+def _named_stream(name, device):
+    s = _STREAMS.get((name, device))
+    if s is None:
+        s = _STREAMS[name, device] = torch.cuda.Stream(device=device)
+    return s
+
+
 # Weight gradients that go straight into a gradient arena are not needed by anything until the optimizer / the
 # all-reduce, so they run on a SIDE stream next to the data-gradient chain: the two MFMA kernels of a layer fill each
 # other's partial last waves (every launch here has an imperfect tile count for 256 CUs).  ``join_side_stream`` makes
 # the current stream wait for them (called by FusedAdam.step / zero_grad and the reducer).
-_SIDE = {}
-from .config import SCHED
-
-
 def _side_stream(device):
-    s = _SIDE.get(device)
-    if s is None:
-        s = _SIDE[device] = torch.cuda.Stream(device=device)
-    return s
-
-
-_OPT = {}
+    return _named_stream('side', device)
 
 
 def _opt_stream(device):
     """Stream of the generator's optimizer step (runs next to the discriminator's backward)."""
-    s = _OPT.get(device)
-    if s is None:
-        s = _OPT[device] = torch.cuda.Stream(device=device)
-    return s
-
-
-_VGGS = {}
+    return _named_stream('opt', device)
 
 
 def _vgg_stream(device):
     """Stream of the VGG(fake) forward / backward (next to the discriminator passes on the fake image)."""
-    s = _VGGS.get(device)
-    if s is None:
-        s = _VGGS[device] = torch.cuda.Stream(device=device)
-    return s
-
-
-_REAL = {}
+    return _named_stream('vgg', device)
 
 
 def _real_stream(device):
     """Stream of everything that depends only on the REAL image (its discriminator pass, its VGG features) and of that
     branch's backward.  Not the weight-gradient stream: the branch's data-gradient chain must not queue behind the
     generator's last weight gradients at the end of the step (r03b trace: 4 ms of idle main stream)."""
-    s = _REAL.get(device)
-    if s is None:
-        s = _REAL[device] = torch.cuda.Stream(device=device)
-    return s
-
-
-_DOPT = {}
+    return _named_stream('real', device)
 
 
 def _d_opt_stream(device):
     """Stream of the discriminator's gradient exchange + optimizer step in data-parallel runs (hidden under the NEXT
     step's input encoding and generator forward)."""
-    s = _DOPT.get(device)
-    if s is None:
-        s = _DOPT[device] = torch.cuda.Stream(device=device)
-    return s
+    return _named_stream('d_opt', device)
+
+
+def _side_streams(device=None):
+    """(device, side stream) of every device that has one (``device``: that one only)."""
+    return [(dev, s) for (name, dev), s in _STREAMS.items() if name == 'side' and (device is None or dev == device)]
 
 
 # Weight-gradient routing: by default every weight gradient goes to the one side stream.  A trainer may route the weight
@@ -147,13 +133,12 @@ class route_wgrads(object):
 def wgrad_waitables(device):
     """What a consumer of ``device``'s weight gradients must wait for: the side stream, and the event behind the last
     launch on every stream weight gradients were routed to.  -> (streams, events)"""
-    return ([s for dev, s in _SIDE.items() if dev == device], list(_WGRAD_USED.get(device, {}).values()))
+    return ([s for _, s in _side_streams(device)], list(_WGRAD_USED.get(device, {}).values()))
 
 
 def join_side_stream(device=None):
-    for dev, s in _SIDE.items():
-        if device is None or dev == device:
-            torch.cuda.current_stream(dev).wait_stream(s)
+    for dev, s in _side_streams(device):
+        torch.cuda.current_stream(dev).wait_stream(s)
     for dev, used in _WGRAD_USED.items():
         if device is None or dev == device:
             cur = torch.cuda.current_stream(dev)
@@ -2178,6 +2163,107 @@ def div_scalar(W, sigma):
     return _DivScalar.apply(W, sigma)
 
 
+# -- plumbing shared by the operators below (none of them is on the training path): cached scratch, status read-back,
+# plane check --------------------------------------------------------------------------------------------------------------
+_SCRATCH = {}           # (operator, device index) -> _Scratch
+
+
+class _Scratch(object):
+    """The cached workspace of one operator on one device: ONE grow-only byte buffer, whatever shapes the operator is
+    called with, so what an operator holds is bounded by its largest call.  ``buf``: the uint8 tensor; ``stream`` /
+    ``event``: the stream of the last use and the event recorded behind it; ``home``: the stream ``buf`` was allocated
+    on."""
+    __slots__ = ('buf', 'home', 'stream', 'event')
+
+    def __init__(self):
+        self.buf = self.home = self.stream = None
+        self.event = torch.cuda.Event()
+
+    def __enter__(self):
+        return self.buf
+
+    def __exit__(self, *a):
+        self.done(self.stream)
+        return False
+
+    def done(self, stream):
+        """Everything queued on ``stream`` so far is the last use."""
+        self.stream = stream
+        self.event.record(stream)
+
+
+def _scratch(tag, nbytes):
+    """``with _scratch(tag, nbytes) as ws:`` -- at least ``nbytes`` (and at least one) bytes of the operator ``tag`` on
+    the current device, handed over to the current stream: a use on another stream than the last one first waits for the
+    event behind that one; leaving the block records the event behind this use.  ``_p(ws)`` and ``ws.numel()`` go to the
+    C ABI.  The base is aligned for fp64 (and more): the caching allocator hands out multiples of 512 bytes."""
+    key = (tag, torch.cuda.current_device())
+    s = _SCRATCH.get(key)
+    if s is None:
+        s = _SCRATCH[key] = _Scratch()
+    cur = torch.cuda.current_stream()
+    if s.stream is not None and s.stream != cur:
+        cur.wait_event(s.event)
+    if s.buf is None or s.buf.numel() < nbytes:
+        # the buffer dropped here is safe to reuse: its block returns to the stream it was allocated on, which either
+        # ran its last launch or was told about the stream that did (record_stream below)
+        s.buf, s.home = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device='cuda'), cur
+        assert s.buf.data_ptr() % 16 == 0
+    elif cur != s.home:
+        # a launch on a stream the allocator does not know of: without this a buffer dropped on growth (or with the
+        # cache) could be handed out again on ``home`` while that launch still runs
+        s.buf.record_stream(cur)
+    s.stream = cur
+    return s
+
+
+def _read_back(tag, st):
+    """The host array of the ``out`` tensor of a ``*_launch`` state: one asynchronous copy into its pinned ``host`` twin,
+    the operator's event recorded behind it (the next launch, which overwrites ``out``, waits for the copy from whatever
+    stream it comes) and one wait on the current stream only."""
+    with torch.cuda.device(st['out'].device):
+        cur = torch.cuda.current_stream()
+        st['host'].copy_(st['out'], non_blocking=True)
+        _SCRATCH[tag, torch.cuda.current_device()].done(cur)
+        cur.synchronize()
+    return st['host'].numpy()
+
+
+# accepted layouts of ``_planes``: name -> (the shapes as the message lists them, rank of what it returns, whether the
+# message shows a refused shape as given or as planes)
+_PLANE_LAYOUTS = {'plane': ('one (H, W) plane', 2, True),
+                  'hw_first': ('(H, W), (B, H, W) or (B, 1, H, W)', 3, True),
+                  'planes': ('(B, H, W), (B, 1, H, W) or (H, W)', 3, False),
+                  'nchw': ('(B, 1, H, W), (B, H, W) or (H, W)', 4, False)}
+
+
+def _planes(op, arg, t, kinds, layout, *, channels=False, max_side=None, single=False):
+    """The argument ``arg`` of the operator ``op`` as contiguous planes: a device tensor of a dtype among ``kinds`` in
+    one of the shapes of ``layout``, reshaped to (H, W), (B, H, W) or (B, 1, H, W).  ``channels``: (B, C, H, W) passes
+    too (scores); ``max_side``: the largest H and W; ``single``: B must be 1 and the plane (H, W) is returned.
+    ValueError for anything else."""
+    name = '%s: %s' % (op, arg)
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('%s must be a device tensor' % name)
+    if t.dtype not in kinds:
+        raise ValueError('%s is %s, accepted: %s' % (name, t.dtype, ' / '.join(str(k) for k in kinds)))
+    accepts, rank, got_given = _PLANE_LAYOUTS[layout]
+    shape = tuple(t.shape)
+    if rank == 2:
+        fits, new = len(shape) >= 2 and all(s == 1 for s in shape[:-2]), shape[-2:]
+    else:
+        fits = len(shape) in (2, 3) or (len(shape) == 4 and (channels or shape[1] == 1))
+        lead = (shape[0] if len(shape) > 2 else 1,) + ((shape[1] if len(shape) == 4 else 1,) if rank == 4 else ())
+        new = lead + shape[-2:]
+    if not fits or 0 in shape or (max_side is not None and max(new[-2:]) > max_side):
+        if max_side is not None:
+            accepts += ' with H, W <= %d' % max_side
+        raise ValueError('%s must be %s, got %s' % (name, accepts, shape if got_given or not fits else new))
+    if single and new[0] != 1:
+        raise ValueError('%s: one plane at a time (B = 1), got %s' % (op, shape))
+    return t.detach().reshape(new[1:] if single else new).contiguous()
+
+
 # -- joint box -> layout -> image edit: evaluate(target_size) and the canvas crop / paste (include/him.h) ---------------
 def resize_compose(comb_prob, obj_prob, label, mask_out, cls, background, align_corners=False):
     """TwoStreamAE_mask.evaluate(target_size)'s tail (reference :318-335) in one kernel at the (H, W) of ``label``
@@ -2359,7 +2445,6 @@ def canvas_paste_blend(patch, box, canvas, x0, y0, H, W, pre=0, feather=8, reach
 # -- seamless (gradient-domain) composite: the membrane of include/him.h "Seamless canvas composite" ---------------------
 MEMBRANE_MAX_N, MEMBRANE_NO_SIDE = 2048, 1
 _MEMBRANE_BASES = {}    # (n, lo, hi, device index) -> (V, Vt, lam) fp64
-_MEMBRANE_WS = {}       # (H, W, sides, device index) -> cached workspace; one stream at a time per shape
 
 
 def membrane_sides(Hc, Wc, x0, y0, H, W, what='membrane'):
@@ -2426,13 +2511,9 @@ def membrane_solve(canvas, x0, y0, P):
         return m, status
     Vy, Vyt, lamy = membrane_basis(ny, t, b, dev)
     Vx, Vxt, lamx = membrane_basis(nx, l, r, dev)
-    key = (H, W, sides, torch.cuda.current_device())
-    ws = _MEMBRANE_WS.get(key)
-    if ws is None:
-        ws = _MEMBRANE_WS[key] = torch.empty(max(int(lib.him_membrane_ws(H, W, sides)) // 8, 1), dtype=torch.float64,
-                                             device=dev)
-    lib.him_membrane_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), _p(Vy), _p(Vyt), _p(lamy), _p(Vx), _p(Vxt), _p(lamx),
-                           _p(m), _p(ws), _p(status), _stream())
+    with _scratch('membrane_solve', lib.him_membrane_ws(H, W, sides)) as ws:
+        lib.him_membrane_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), _p(Vy), _p(Vyt), _p(lamy), _p(Vx), _p(Vxt),
+                               _p(lamx), _p(m), _p(ws), _p(status), _stream())
     return m, status
 
 
@@ -2490,7 +2571,6 @@ def canvas_paste_seamless(cropped, box, canvas, x0, y0, H, W, pre, *, feather=No
 # -- region Poisson clone: include/him.h "Region Poisson clone" -----------------------------------------------------------
 REGION_POISSON_MAX_N, REGION_POISSON_MAX_ITER = 2048, 1 << 20
 REGION_POISSON_EMPTY, REGION_POISSON_SINGULAR, REGION_POISSON_MAX_ITER_HIT, REGION_POISSON_NONFINITE = 1, 2, 4, 8
-_REGION_POISSON_WS = {}  # (H, W, device index) -> cached workspace; one stream at a time per shape
 
 
 def region_poisson_args(H, W, mixed, rtol, max_iter, what='region_poisson'):
@@ -2551,13 +2631,9 @@ def region_poisson_solve(canvas, x0, y0, P, region, *, mixed=False, rtol=1e-7, m
         u = torch.empty((1, 3, H, W), dtype=torch.float64, device=dev)
         status = torch.empty(8, dtype=torch.int32, device=dev)
         resid = torch.empty(3, dtype=torch.float64, device=dev)
-        key = (H, W, dev.index)
-        ws = _REGION_POISSON_WS.get(key)
-        if ws is None:
-            ws = _REGION_POISSON_WS[key] = torch.empty(int(lib.him_region_poisson_ws(H, W)) // 8, dtype=torch.float64,
-                                                       device=dev)
-        lib.him_region_poisson_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), _p(region), mixed, rtol, max_iter, _p(u),
-                                     _p(status), _p(resid), _p(ws), ws.numel() * 8, _stream())
+        with _scratch(what, lib.him_region_poisson_ws(H, W)) as ws:
+            lib.him_region_poisson_solve(_p(canvas), Hc, Wc, x0, y0, H, W, _p(P), _p(region), mixed, rtol, max_iter, _p(u),
+                                         _p(status), _p(resid), _p(ws), ws.numel(), _stream())
     return u, status, resid
 
 
@@ -2720,24 +2796,14 @@ _CLS_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
 _INST_FLAGS = ((1, 'more than max_objects=%(max)d objects (%(count)d found)'),
                (2, 'an instance id outside 0..65535'),
                (4, 'a class value outside 0..255 (or not integral)'))
-_INST_STATE = {}        # (H, W, max_objects, device index) -> workspace, status + table, pinned host copy, event, stream
-
-
-def _inst_plane(t, what, kinds):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError('inst_summary: %s must be a device tensor' % what)
-    if t.dtype not in kinds:
-        raise ValueError('inst_summary: %s is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in kinds)))
-    if t.dim() < 2 or any(s != 1 for s in t.shape[:-2]) or 0 in t.shape:
-        raise ValueError('inst_summary: %s must be one (H, W) plane, got %s' % (what, tuple(t.shape)))
-    return t.detach().reshape(t.shape[-2], t.shape[-1]).contiguous()
+_INST_STATE = {}        # (H, W, max_objects, device index) -> status + table, pinned host copy
 
 
 def inst_summary_launch(inst, cls, min_id=1000, max_objects=1024):
     """Queue the device pass on the current stream; returns the cached state whose ``out`` tensor (2 status ints, then
     ``max_objects`` rows of 7) the kernels fill.  No copy, no host synchronisation (``inst_summary`` adds both)."""
-    inst = _inst_plane(inst, 'inst', _INST_KINDS)
-    cls = _inst_plane(cls, 'cls', _CLS_KINDS)
+    inst = _planes('inst_summary', 'inst', inst, _INST_KINDS, 'plane')
+    cls = _planes('inst_summary', 'cls', cls, _CLS_KINDS, 'plane')
     if inst.shape != cls.shape or inst.device != cls.device:
         raise ValueError('inst_summary: inst %s on %s and cls %s on %s differ' % (tuple(inst.shape), inst.device,
                                                                                 tuple(cls.shape), cls.device))
@@ -2749,19 +2815,13 @@ def inst_summary_launch(inst, cls, min_id=1000, max_objects=1024):
         key = (H, W, max_objects, torch.cuda.current_device())
         st = _INST_STATE.get(key)
         if st is None:
-            nws = int(lib.him_inst_summary_workspace(H, W, max_objects))
             st = _INST_STATE[key] = dict(
-                ws=torch.empty(nws, dtype=torch.uint8, device=inst.device), nws=nws,
                 out=torch.empty(2 + 7 * max_objects, dtype=torch.int32, device=inst.device),
-                host=torch.empty(2 + 7 * max_objects, dtype=torch.int32, pin_memory=True),
-                event=torch.cuda.Event(), stream=None)
-        elif st['stream'] != _stream():
-            torch.cuda.current_stream().wait_event(st['event'])      # the previous user of this workspace, elsewhere
+                host=torch.empty(2 + 7 * max_objects, dtype=torch.int32, pin_memory=True))
         out = st['out']
-        lib.him_inst_summary(_p(inst), _INST_KINDS[inst.dtype], _p(cls), _CLS_KINDS[cls.dtype], H, W, int(min_id),
-                             max_objects, _p(out), _p(out) + 8, _p(st['ws']), st['nws'], _stream())
-        st['stream'] = _stream()
-        st['event'].record(torch.cuda.current_stream())
+        with _scratch('inst_summary', lib.him_inst_summary_workspace(H, W, max_objects)) as ws:
+            lib.him_inst_summary(_p(inst), _INST_KINDS[inst.dtype], _p(cls), _CLS_KINDS[cls.dtype], H, W, int(min_id),
+                                 max_objects, _p(out), _p(out) + 8, _p(ws), ws.numel(), _stream())
     return st
 
 
@@ -2771,12 +2831,7 @@ def inst_summary(inst, cls, min_id=1000, max_objects=1024):
     inclusive, ``cls = int(np.median(cls[inst == id]))`` of the device plane ``cls`` (uint8 / int32 / int64 / integral
     fp32, 0..255) -- what upstream's ``construct_box`` stores per object.  One asynchronous copy of status + table into a
     pinned buffer and one wait on the current stream.  ``ValueError`` names an overflow or a value outside its domain."""
-    st = inst_summary_launch(inst, cls, min_id, max_objects)
-    with torch.cuda.device(st['out'].device):
-        st['host'].copy_(st['out'], non_blocking=True)
-        st['event'].record(torch.cuda.current_stream())
-        torch.cuda.current_stream().synchronize()
-    host = st['host'].numpy()
+    host = _read_back('inst_summary', inst_summary_launch(inst, cls, min_id, max_objects))
     count, flags = int(host[0]), int(host[1])
     if flags:
         why = [text % dict(max=int(max_objects), count=count) for bit, text in _INST_FLAGS if flags & bit]
@@ -2790,7 +2845,7 @@ CCL_OVERFLOW, CCL_CLS_RANGE = 1, 2
 _CCL_FLAGS = ((CCL_OVERFLOW, 'plane %(plane)d: %(count)d objects, more than max_objects=%(max)d or than the ids '
                              '%(base)d..65535 hold'),
               (CCL_CLS_RANGE, 'plane %(plane)d: a class value outside 0..255 (or not integral)'))
-_CCL_STATE = {}         # (B, H, W, device index) -> workspace, status, pinned host copy, event, stream, things -> table
+_CCL_STATE = {}         # (B, H, W, device index) -> status, pinned host copy, things -> table
 
 
 def _ccl_things(things):
@@ -2804,21 +2859,6 @@ def _ccl_things(things):
     return ids
 
 
-def _ccl_planes(label):
-    if not torch.is_tensor(label) or not label.is_cuda:
-        raise ValueError('label_instances: label must be a device tensor')
-    if label.dtype not in _CLS_KINDS:
-        raise ValueError('label_instances: label is %s, accepted: %s' % (label.dtype,
-                                                                         ' / '.join(str(k) for k in _CLS_KINDS)))
-    ok = label.dim() in (2, 3) or (label.dim() == 4 and label.shape[1] == 1)
-    if not ok or 0 in label.shape:
-        raise ValueError('label_instances: label must be (H, W), (B, H, W) or (B, 1, H, W), got %s' % (tuple(label.shape),))
-    H, W = label.shape[-2:]
-    if H * W > 0x7fffffff:
-        raise ValueError('label_instances: %d x %d pixels (at most 2^31 - 1)' % (H, W))
-    return label.detach().reshape(-1, H, W).contiguous()
-
-
 def label_instances_launch(label, things, connectivity=4, min_area=1, base_id=1000, max_objects=1024):
     """Queue the labelling of one (H, W) plane or a (B, H, W) / (B, 1, H, W) batch of class planes on the current stream;
     returns ``(inst, counts, state)``: a fresh int32 device tensor of the input's shape, the device view of the per-plane
@@ -2826,8 +2866,10 @@ def label_instances_launch(label, things, connectivity=4, min_area=1, base_id=10
     copy, no host synchronisation (``label_instances`` adds both).  ``counts`` and ``out`` are overwritten by the next
     launch of the same batch shape on that device."""
     ids = _ccl_things(things)
-    planes = _ccl_planes(label)
+    planes = _planes('label_instances', 'label', label, _CLS_KINDS, 'hw_first')
     B, H, W = planes.shape
+    if H * W > 0x7fffffff:
+        raise ValueError('label_instances: %d x %d pixels (at most 2^31 - 1)' % (H, W))
     connectivity, min_area, base_id, max_objects = int(connectivity), int(min_area), int(base_id), int(max_objects)
     if connectivity not in (4, 8):
         raise ValueError('label_instances: connectivity must be 4 or 8, got %d' % connectivity)
@@ -2838,17 +2880,13 @@ def label_instances_launch(label, things, connectivity=4, min_area=1, base_id=10
     with torch.cuda.device(planes.device):
         key = (B, H, W, torch.cuda.current_device())
         st = _CCL_STATE.get(key)
+        nws = lib.him_label_instances_workspace(B, H, W)
+        if nws == 0:
+            raise ValueError('label_instances: a batch of %d planes of %d x %d is too large' % (B, H, W))
         if st is None:
-            nws = int(lib.him_label_instances_workspace(B, H, W))
-            if nws == 0:
-                raise ValueError('label_instances: a batch of %d planes of %d x %d is too large' % (B, H, W))
             st = _CCL_STATE[key] = dict(
-                ws=torch.empty(nws, dtype=torch.uint8, device=planes.device), nws=nws,
                 out=torch.empty((B, 2), dtype=torch.int32, device=planes.device),
-                host=torch.empty((B, 2), dtype=torch.int32, pin_memory=True),
-                event=torch.cuda.Event(), stream=None, things={})
-        elif st['stream'] != _stream():
-            torch.cuda.current_stream().wait_event(st['event'])      # the previous user of this workspace, elsewhere
+                host=torch.empty((B, 2), dtype=torch.int32, pin_memory=True), things={})
         table = st['things'].get(ids)
         if table is None:
             host = torch.zeros(256, dtype=torch.uint8)
@@ -2856,10 +2894,9 @@ def label_instances_launch(label, things, connectivity=4, min_area=1, base_id=10
                 host[list(ids)] = 1
             table = st['things'][ids] = host.to(planes.device)
         inst = torch.empty(label.shape, dtype=torch.int32, device=planes.device)
-        lib.him_label_instances(_p(planes), _CLS_KINDS[planes.dtype], B, H, W, _p(table), connectivity, min_area, base_id,
-                                max_objects, _p(inst), _p(st['out']), _p(st['ws']), st['nws'], _stream())
-        st['stream'] = _stream()
-        st['event'].record(torch.cuda.current_stream())
+        with _scratch('label_instances', nws) as ws:
+            lib.him_label_instances(_p(planes), _CLS_KINDS[planes.dtype], B, H, W, _p(table), connectivity, min_area,
+                                    base_id, max_objects, _p(inst), _p(st['out']), _p(ws), ws.numel(), _stream())
     return inst, st['out'][:, 0], st
 
 
@@ -2872,11 +2909,7 @@ def label_instances(label, things, connectivity=4, min_area=1, base_id=1000, max
     asynchronous copy of the status into a pinned buffer and one wait on the current stream.  ``ValueError`` names an
     overflow or a class outside its domain."""
     inst, _, st = label_instances_launch(label, things, connectivity, min_area, base_id, max_objects)
-    with torch.cuda.device(inst.device):
-        st['host'].copy_(st['out'], non_blocking=True)
-        st['event'].record(torch.cuda.current_stream())
-        torch.cuda.current_stream().synchronize()
-    host = st['host'].numpy().copy()
+    host = _read_back('label_instances', st).copy()
     why = [text % dict(plane=b, count=int(host[b, 0]), max=int(max_objects), base=int(base_id))
            for b in range(host.shape[0]) for bit, text in _CCL_FLAGS if int(host[b, 1]) & bit]
     if why:
@@ -2885,7 +2918,7 @@ def label_instances(label, things, connectivity=4, min_area=1, base_id=1000, max
 
 
 # -- ADE20K segmentation decode: preprocess_ade's per-image work in one device call (include/him.h) ---------------------
-_ADE_STATE = {}         # device index -> workspace, status + table, pinned host copy, event, stream, keep tuple -> tensor
+_ADE_STATE = {}         # device index -> status + table, pinned host copy, keep tuple -> tensor
 
 
 def _ade_keep(keep):
@@ -2935,14 +2968,9 @@ def ade_decode_launch(seg, keep, want_cls=False):
         key = torch.cuda.current_device()
         st = _ADE_STATE.get(key)
         if st is None:
-            nws = int(lib.him_ade_decode_workspace())
             st = _ADE_STATE[key] = dict(
-                ws=torch.empty(nws, dtype=torch.uint8, device=seg.device), nws=nws,
                 out=torch.empty(2 + 7 * 256, dtype=torch.int32, device=seg.device),
-                host=torch.empty(2 + 7 * 256, dtype=torch.int32, pin_memory=True),
-                event=torch.cuda.Event(), stream=None, keep={})
-        elif st['stream'] != _stream():
-            torch.cuda.current_stream().wait_event(st['event'])      # the previous user of this workspace, elsewhere
+                host=torch.empty(2 + 7 * 256, dtype=torch.int32, pin_memory=True), keep={})
         kdev = st['keep'].get(ids)
         if kdev is None:
             import numpy as np
@@ -2951,10 +2979,9 @@ def ade_decode_launch(seg, keep, want_cls=False):
         inst = torch.empty((H, W), dtype=torch.uint8, device=seg.device)
         cls = torch.empty((H, W), dtype=torch.uint16, device=seg.device) if want_cls else None
         out = st['out']
-        lib.him_ade_decode(_p(seg), H, W, pb, _p(kdev), len(ids), _p(cls) if want_cls else 0, _p(label), _p(inst),
-                           _p(out), _p(out) + 8, _p(st['ws']), st['nws'], _stream())
-        st['stream'] = _stream()
-        st['event'].record(torch.cuda.current_stream())
+        with _scratch('ade_decode', lib.him_ade_decode_workspace()) as ws:
+            lib.him_ade_decode(_p(seg), H, W, pb, _p(kdev), len(ids), _p(cls) if want_cls else 0, _p(label), _p(inst),
+                               _p(out), _p(out) + 8, _p(ws), ws.numel(), _stream())
     return label, inst, cls, st
 
 
@@ -2966,19 +2993,13 @@ def ade_decode(seg, keep, want_cls=False):
     (``want_cls``) the raw classes as a uint16 device plane.  One asynchronous copy of status + table into a pinned buffer
     and one wait on the current stream.  ``ValueError`` for a ``seg`` or a ``keep`` outside the contract."""
     label, inst, cls, st = ade_decode_launch(seg, keep, want_cls)
-    with torch.cuda.device(st['out'].device):
-        st['host'].copy_(st['out'], non_blocking=True)
-        st['event'].record(torch.cuda.current_stream())
-        torch.cuda.current_stream().synchronize()
-    host = st['host'].numpy()
+    host = _read_back('ade_decode', st)
     count = int(host[0])
     rows = host[2:2 + 7 * count].reshape(count, 7).copy()
     return (label, inst, rows, cls) if want_cls else (label, inst, rows)
 
 
 # -- evaluation metrics: SSIM / error sums and the confusion matrix in one device call each (include/him.h) -------------
-_MET_WS = {}            # (B, C, H, W, device index) -> workspace of him_image_metrics
-_CONF_WS = {}           # (n, device index) -> workspace of him_confusion
 _PRED_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
 CONF_SKIPPED, CONF_SATURATED = 1, 2
 
@@ -3000,8 +3021,7 @@ def image_metrics(a, b, *, scale, offset, quantize, data_range, box=None, want_m
     [sum of SSIM over the windows, windows, sum of squared error, sum of absolute error, pixels] per plane after the
     mapping ``x * scale + offset`` (and ``trunc(clip(., 0, 255))`` with ``quantize``); ``map`` the (B, C, H-10, W-10)
     SSIM map with ``want_map`` (whole-image calls only), else None.  ``box``: (B, 4) int32 device tensor of inclusive
-    ``(xmin, ymin, xmax, ymax)``, or None.  Current stream, no host synchronisation.  The workspace is cached per shape
-    and device and is not guarded by events: calls of one shape must be queued on one stream at a time."""
+    ``(xmin, ymin, xmax, ymax)``, or None.  Current stream, no host synchronisation."""
     a, b = _metric_image(a, 'a'), _metric_image(b, 'b')
     if a.shape != b.shape or a.device != b.device:
         raise ValueError('image_metrics: a %s on %s and b %s on %s differ' % (tuple(a.shape), a.device, tuple(b.shape),
@@ -3016,30 +3036,12 @@ def image_metrics(a, b, *, scale, offset, quantize, data_range, box=None, want_m
     if want_map and (H < 11 or W < 11):
         raise ValueError('image_metrics: no 11x11 window fits a %dx%d image' % (H, W))
     with torch.cuda.device(a.device):
-        key = (B, C, H, W, torch.cuda.current_device())
-        ws = _MET_WS.get(key)
-        if ws is None:
-            ws = _MET_WS[key] = torch.empty(max(int(lib.him_image_metrics_workspace(B, C, H, W)) // 8, 1),
-                                            dtype=torch.float64, device=a.device)
         sums = torch.empty((B, C, 5), dtype=torch.float64, device=a.device)
         smap = torch.empty((B, C, H - 10, W - 10), dtype=torch.float32, device=a.device) if want_map else None
-        lib.him_image_metrics(_p(a), _p(b), B, C, H, W, float(scale), float(offset), 1 if quantize else 0,
-                              float(data_range), _p(box), _p(sums), _p(smap), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('image_metrics', lib.him_image_metrics_workspace(B, C, H, W)) as ws:
+            lib.him_image_metrics(_p(a), _p(b), B, C, H, W, float(scale), float(offset), 1 if quantize else 0,
+                                  float(data_range), _p(box), _p(sums), _p(smap), _p(ws), ws.numel(), _stream())
     return sums, smap
-
-
-def _label_planes(t, what, kinds, scores=False):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError('confusion: %s must be a device tensor' % what)
-    if t.dtype not in kinds:
-        raise ValueError('confusion: %s is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in kinds)))
-    if t.dim() == 2:
-        t = t[None, None]
-    elif t.dim() == 3:
-        t = t.unsqueeze(1)
-    if t.dim() != 4 or 0 in t.shape or (t.shape[1] != 1 and not scores):
-        raise ValueError('confusion: %s must be (B, 1, H, W), (B, H, W) or (H, W), got %s' % (what, tuple(t.shape)))
-    return t.detach().contiguous()
 
 
 def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, pred_kind=None):
@@ -3047,10 +3049,9 @@ def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, 
     column = prediction) and the 2-int status record (skipped pixels, flag bits), both on the device.  ``pred``: uint8 /
     int32 / int64 / integral fp32 ids, or fp32 scores (B, C > 1, H, W) (arg-max, lowest channel on a tie), or with
     ``pred_kind='prob'`` fp32 probabilities thresholded at 0.5.  ``mask``: fp32, pixels count where it is not 0.
-    ``out``: the pair an earlier call returned; the call then adds into it.  Current stream, no host synchronisation.  The
-    workspace is cached per ``n`` and device: calls with one ``n`` must be queued on one stream at a time."""
-    gt = _label_planes(gt, 'gt', _PRED_KINDS)
-    pred = _label_planes(pred, 'pred', _PRED_KINDS, scores=True)
+    ``out``: the pair an earlier call returned; the call then adds into it.  Current stream, no host synchronisation."""
+    gt = _planes('confusion', 'gt', gt, _PRED_KINDS, 'nchw')
+    pred = _planes('confusion', 'pred', pred, _PRED_KINDS, 'nchw', channels=True)
     if pred_kind == 'prob':
         kind = 5
     elif pred_kind == 'scores' or (pred_kind is None and pred.dtype == torch.float32 and pred.shape[1] > 1):
@@ -3067,7 +3068,7 @@ def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, 
     if tuple(gt.shape) != (B, 1, H, W) or gt.device != pred.device:
         raise ValueError('confusion: pred %s and gt %s differ' % (tuple(pred.shape), tuple(gt.shape)))
     if mask is not None:
-        mask = _label_planes(mask, 'mask', (torch.float32,))
+        mask = _planes('confusion', 'mask', mask, (torch.float32,), 'nchw')
         if tuple(mask.shape) != (B, 1, H, W) or mask.device != pred.device:
             raise ValueError('confusion: mask %s does not fit pred %s' % (tuple(mask.shape), tuple(pred.shape)))
     n = int(n)
@@ -3075,11 +3076,6 @@ def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, 
         raise ValueError('confusion: n must be in 1..256, got %d' % n)
     rows = B if per_sample else 1
     with torch.cuda.device(pred.device):
-        key = (n, torch.cuda.current_device())
-        ws = _CONF_WS.get(key)
-        if ws is None:
-            ws = _CONF_WS[key] = torch.empty(max(int(lib.him_confusion_workspace(n)) // 8, 1), dtype=torch.int64,
-                                             device=pred.device)
         if out is None:
             counts = torch.empty((rows, n, n), dtype=torch.int64, device=pred.device)
             status = torch.empty(2, dtype=torch.int32, device=pred.device)
@@ -3089,32 +3085,16 @@ def confusion(pred, gt, n, *, mask=None, ignore=-1, per_sample=False, out=None, 
                     or counts.device != pred.device or status.dtype != torch.int32 or status.numel() != 2:
                 raise ValueError('confusion: out must be the (counts (%d, %d, %d) int64, status (2,) int32) pair of an '
                                  'earlier call' % (rows, n, n))
-        lib.him_confusion(_p(pred), kind, _p(gt), _PRED_KINDS[gt.dtype], _p(mask), B, C, H, W, n, int(ignore),
-                          1 if per_sample else 0, 0 if out is None else 1, _p(counts), _p(status), _p(ws),
-                          ws.numel() * 8, _stream())
+        with _scratch('confusion', lib.him_confusion_workspace(n)) as ws:
+            lib.him_confusion(_p(pred), kind, _p(gt), _PRED_KINDS[gt.dtype], _p(mask), B, C, H, W, n, int(ignore),
+                              1 if per_sample else 0, 0 if out is None else 1, _p(counts), _p(status), _p(ws),
+                              ws.numel(), _stream())
     return counts, status
 
 
 # -- distance transform and boundary statistics (include/him.h "Distance transform and boundary metrics") --------------
-_EDT_WS = {}            # (K, H, W, device index) -> workspace of him_edt
-_BSTAT_WS = {}          # (K, H, W, device index) -> workspace of him_boundary_stats
 EDT_RULES = {'nonzero': 0, 'equals': 1, 'boundary_of': 2, 'any_boundary': 3}
-EDT_NONE, EDT_BAD_JOB = 2 ** 31 - 1, 1
-
-
-def _edt_planes(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError('%s: src must be a device tensor' % what)
-    if t.dtype not in _PRED_KINDS:
-        raise ValueError('%s: src is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in _PRED_KINDS)))
-    if t.dim() == 2:
-        t = t[None]
-    elif t.dim() == 4 and t.shape[1] == 1:
-        t = t[:, 0]
-    if t.dim() != 3 or 0 in t.shape or max(t.shape[1:]) > 16384:
-        raise ValueError('%s: src must be (B, H, W), (B, 1, H, W) or (H, W) with H, W <= 16384, got %s'
-                         % (what, tuple(t.shape)))
-    return t.detach().contiguous()
+EDT_NONE, EDT_BAD_JOB, _EDT_MAX_SIDE = 2 ** 31 - 1, 1, 16384
 
 
 def _edt_jobs(jobs, device, what):
@@ -3144,9 +3124,8 @@ def distance_transform(src, jobs=None, value=None, rule='nonzero', want_nearest=
     equidistant ones; -1 without a seed) and the (K, 2) record [seed count, flag bits].  ``src``: uint8 / int32 / int64 /
     integral fp32 ids, (B, H, W).  ``jobs``: a (K, 3) int32 device table [plane, value, rule number]; None runs one job
     per plane with ``rule`` in ``EDT_RULES`` and ``value``.  ``EDT_NONE`` marks a job without a seed.  Current stream,
-    no host synchronisation, no autograd.  The workspace is cached per (K, H, W) and device: calls of one shape must be
-    queued on one stream at a time."""
-    src = _edt_planes(src, 'distance_transform')
+    no host synchronisation, no autograd."""
+    src = _planes('distance_transform', 'src', src, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE)
     B, H, W = src.shape
     if jobs is None:
         if rule not in EDT_RULES:
@@ -3155,16 +3134,12 @@ def distance_transform(src, jobs=None, value=None, rule='nonzero', want_nearest=
     jobs = _edt_jobs(jobs, src.device, 'distance_transform')
     K = jobs.shape[0]
     with torch.cuda.device(src.device):
-        key = (K, H, W, torch.cuda.current_device())
-        ws = _EDT_WS.get(key)
-        if ws is None:
-            ws = _EDT_WS[key] = torch.empty(max(int(lib.him_edt_workspace(K, H, W)) // 2, 1), dtype=torch.int16,
-                                            device=src.device)
         dist2 = torch.empty((K, H, W), dtype=torch.int32, device=src.device)
         nearest = torch.empty((K, H, W), dtype=torch.int32, device=src.device) if want_nearest else None
         status = torch.empty((K, 2), dtype=torch.int32, device=src.device)
-        lib.him_edt(_p(src), _PRED_KINDS[src.dtype], B, H, W, _p(jobs), K, _p(dist2), _p(nearest), _p(status), _p(ws),
-                    ws.numel() * 2, _stream())
+        with _scratch('distance_transform', lib.him_edt_workspace(K, H, W)) as ws:
+            lib.him_edt(_p(src), _PRED_KINDS[src.dtype], B, H, W, _p(jobs), K, _p(dist2), _p(nearest), _p(status), _p(ws),
+                        ws.numel(), _stream())
     return dist2, nearest, status
 
 
@@ -3173,7 +3148,7 @@ def boundary_stats(src, jobs, dist2, tol2):
     ``dist2 <= tol2``, the largest reachable ``dist2`` (-1: none), seeds with ``dist2 == EDT_NONE``] and the float64 (K,)
     sum of ``sqrt(dist2)`` over the reachable seeds, added in a fixed order.  ``dist2``: the (K, H, W) result of
     ``distance_transform`` over the other map with the same job table.  Current stream, no host synchronisation."""
-    src = _edt_planes(src, 'boundary_stats')
+    src = _planes('boundary_stats', 'src', src, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE)
     B, H, W = src.shape
     jobs = _edt_jobs(jobs, src.device, 'boundary_stats')
     K = jobs.shape[0]
@@ -3185,15 +3160,11 @@ def boundary_stats(src, jobs, dist2, tol2):
         raise ValueError('boundary_stats: tol2 must not be negative, got %d' % tol2)
     dist2 = dist2.contiguous()
     with torch.cuda.device(src.device):
-        key = (K, H, W, torch.cuda.current_device())
-        ws = _BSTAT_WS.get(key)
-        if ws is None:
-            ws = _BSTAT_WS[key] = torch.empty(max(int(lib.him_boundary_stats_workspace(K, H, W)) // 8, 1),
-                                              dtype=torch.int64, device=src.device)
         counts = torch.empty((K, 4), dtype=torch.int64, device=src.device)
         sumd = torch.empty(K, dtype=torch.float64, device=src.device)
-        lib.him_boundary_stats(_p(src), _PRED_KINDS[src.dtype], B, H, W, _p(jobs), K, _p(dist2), tol2, _p(counts),
-                               _p(sumd), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('boundary_stats', lib.him_boundary_stats_workspace(K, H, W)) as ws:
+            lib.him_boundary_stats(_p(src), _PRED_KINDS[src.dtype], B, H, W, _p(jobs), K, _p(dist2), tol2, _p(counts),
+                                   _p(sumd), _p(ws), ws.numel(), _stream())
     return counts, sumd
 
 
@@ -3202,7 +3173,7 @@ def label_ids(pred, pred_kind):
     the lowest on a tie) or probabilities (B, 1, H, W) (``'prob'``: p > 0.5), the rules of ``confusion``."""
     if pred_kind not in ('scores', 'prob'):
         raise ValueError("label_ids: pred_kind %r ('scores' or 'prob')" % (pred_kind,))
-    pred = _label_planes(pred, 'pred', (torch.float32,), scores=True)
+    pred = _planes('confusion', 'pred', pred, (torch.float32,), 'nchw', channels=True)
     B, C, H, W = pred.shape
     if pred_kind == 'prob' and C != 1:
         raise ValueError('label_ids: probability planes have one channel, got %s' % (tuple(pred.shape),))
@@ -3216,19 +3187,10 @@ def label_ids(pred, pred_kind):
 LAYOUT_NO_SEED, LAYOUT_CLASS_RANGE = 1, 2
 LAYOUT_MAX_CLASS = 65536
 LAYOUT_MAX_COORD = 1 << 20
-_LAYOUT_WS = {}         # (H, W, device index) -> workspace of him_layout_erase
 _LAYOUT_TABLES = {}     # (class ids, n_class, device index) -> device class bit table
 _LAYOUT_INDEX = {}      # (source length, destination length, device index) -> device NEAREST index table
 _LAYOUT_ID_RANGE = {torch.uint8: (0, 255), torch.int32: (-2 ** 31, 2 ** 31 - 1), torch.int64: (-2 ** 31, 2 ** 31 - 1),
                     torch.float32: (-2 ** 24, 2 ** 24)}
-
-
-def _layout_plane(t, what):
-    """One (H, W) plane out of the shapes ``_edt_planes`` takes, B = 1."""
-    planes = _edt_planes(t, what)
-    if planes.shape[0] != 1:
-        raise ValueError('%s: one plane at a time (B = 1), got %s' % (what, tuple(t.shape)))
-    return planes[0]
 
 
 def _layout_int(v, what, lo, hi):
@@ -3297,16 +3259,15 @@ def layout_erase(label, inst, id=None, *, region=None, fill, n_class):
     uint8 / int32 / int64 / integral fp32 device planes, (H, W), (1, H, W) or (1, 1, H, W); the outputs have their dtype
     and shape.  ``changed``: uint8 (H, W), 1 where the label changed.  ``status``: int32 (4,) [|R|, seeds, changed pixels,
     flags]; ``LAYOUT_NO_SEED``: no pixel of an allowed class, the outputs are copies; ``LAYOUT_CLASS_RANGE``: a label
-    outside [0, n_class) was seen (never a seed, never rewritten).  Current stream, no host synchronisation, no autograd.
-    The workspace is cached per (H, W) and device: calls of one shape must be queued on one stream at a time."""
+    outside [0, n_class) was seen (never a seed, never rewritten).  Current stream, no host synchronisation, no autograd."""
     if (id is None) == (region is None):
         raise ValueError('layout_erase: give an instance id or a region plane, not both')
     if region is None:
         id = _layout_int(id, 'layout_erase: id', -2 ** 31, 2 ** 31 - 1)
     n_class = _layout_int(n_class, 'layout_erase: n_class', 1, LAYOUT_MAX_CLASS)
     fill = _layout_classes(fill, n_class, 'layout_erase: fill')
-    lab = _layout_plane(label, 'layout_erase: label')
-    ins = _layout_plane(inst, 'layout_erase: inst')
+    lab = _planes('layout_erase: label', 'src', label, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
+    ins = _planes('layout_erase: inst', 'src', inst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
     if lab.shape != ins.shape or lab.device != ins.device:
         raise ValueError('layout_erase: label %s on %s and inst %s on %s differ' % (tuple(lab.shape), lab.device,
                                                                                  tuple(ins.shape), ins.device))
@@ -3319,17 +3280,13 @@ def layout_erase(label, inst, id=None, *, region=None, fill, n_class):
         id = 0
     table = _layout_table(fill, n_class, lab.device)
     with torch.cuda.device(lab.device):
-        key = (H, W, torch.cuda.current_device())
-        ws = _LAYOUT_WS.get(key)
-        if ws is None:
-            ws = _LAYOUT_WS[key] = torch.empty(max(int(lib.him_layout_erase_workspace(H, W)), 16), dtype=torch.uint8,
-                                               device=lab.device)
         label_out, inst_out = torch.empty_like(lab), torch.empty_like(ins)
         changed = torch.empty((H, W), dtype=torch.uint8, device=lab.device)
         status = torch.empty(4, dtype=torch.int32, device=lab.device)
-        lib.him_layout_erase(_p(lab), _PRED_KINDS[lab.dtype], _p(ins), _PRED_KINDS[ins.dtype], _p(region), id, H, W,
-                             _p(table), n_class, _p(label_out), _p(inst_out), _p(changed), _p(status), _p(ws), ws.numel(),
-                             _stream())
+        with _scratch('layout_erase', lib.him_layout_erase_workspace(H, W)) as ws:
+            lib.him_layout_erase(_p(lab), _PRED_KINDS[lab.dtype], _p(ins), _PRED_KINDS[ins.dtype], _p(region), id, H, W,
+                                 _p(table), n_class, _p(label_out), _p(inst_out), _p(changed), _p(status), _p(ws),
+                                 ws.numel(), _stream())
     return label_out.reshape(label.shape), inst_out.reshape(inst.shape), changed, status
 
 
@@ -3350,9 +3307,9 @@ def layout_place(label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_i
     _layout_int(new_id, 'layout_place: new_id', -2 ** 31, 2 ** 31 - 1)
     prot = _layout_classes(protect, LAYOUT_MAX_CLASS, 'layout_place: protect')
     n_class = prot[-1] + 1 if prot else 1
-    lab = _layout_plane(label_dst, 'layout_place: label_dst')
-    ins = _layout_plane(inst_dst, 'layout_place: inst_dst')
-    src = _layout_plane(inst_src, 'layout_place: inst_src')
+    lab = _planes('layout_place: label_dst', 'src', label_dst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
+    ins = _planes('layout_place: inst_dst', 'src', inst_dst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
+    src = _planes('layout_place: inst_src', 'src', inst_src, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
     if lab.shape != ins.shape or lab.device != ins.device or src.device != lab.device:
         raise ValueError('layout_place: label_dst %s on %s, inst_dst %s on %s and inst_src on %s differ'
                          % (tuple(lab.shape), lab.device, tuple(ins.shape), ins.device, src.device))
@@ -3416,7 +3373,7 @@ def boundary_dist2(planes):
 def surface_dists(t):
     """``(d2_fg, d2_bg)``, int32 (B,H,W) each: squared distances to the nearest pixel with ``t == 1`` and with ``t == 0``
     of the 0/1 mask ``t`` ((B,1,H,W) or (B,H,W)), two 'equals' jobs per sample in one transform."""
-    t = _edt_planes(t, 'surface_dists')
+    t = _planes('surface_dists', 'src', t, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE)
     B, H, W = t.shape
     d2 = distance_transform(t, jobs=edt_jobs(B, [0, 1], 'equals', t.device))[0].view(B, 2, H, W)
     return d2[:, 1].contiguous(), d2[:, 0].contiguous()
@@ -3563,21 +3520,6 @@ def surface_loss(p, t, dists=None):
 # -- panoptic matching: segments, overlaps, unique matches, per-class tp / fp / fn (include/him.h "Panoptic matching") ---
 PQ_OVERFLOW, PQ_ID_RANGE, PQ_CLS_RANGE, PQ_MIXED, PQ_CCL = 1, 2, 4, 8, 16
 _SEG_KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
-_PQ_WS = {}             # (B, max_segments, device index) -> workspace of him_panoptic_match
-
-
-def _pq_planes(t, what, kinds):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError('panoptic_match: %s must be a device tensor' % what)
-    if t.dtype not in kinds:
-        raise ValueError('panoptic_match: %s is %s, accepted: %s' % (what, t.dtype, ' / '.join(str(k) for k in kinds)))
-    if t.dim() == 2:
-        t = t[None]
-    elif t.dim() == 4 and t.shape[1] == 1:
-        t = t[:, 0]
-    if t.dim() != 3 or 0 in t.shape:
-        raise ValueError('panoptic_match: %s must be (B, H, W), (B, 1, H, W) or (H, W), got %s' % (what, tuple(t.shape)))
-    return t.detach().contiguous()
 
 
 def panoptic_match(pred_seg, pred_cls, gt_seg, gt_cls, n_class, *, mask=None, ignore=-1, max_segments=1024, out=None,
@@ -3589,18 +3531,17 @@ def panoptic_match(pred_seg, pred_cls, gt_seg, gt_cls, n_class, *, mask=None, ig
     union of every ground-truth segment.  ``*_seg``: uint8 / int32 / int64 ids 0..65535; ``*_cls``: uint8 / int32 / int64 /
     integral fp32 classes; ``mask``: fp32, void where 0; ``ignore``: a ground-truth class that is void.  ``out``: the
     (counts, iou_sum, status) triple an earlier call returned; the call then adds into it.  Current stream, no host
-    synchronisation.  The workspace is cached per (B, max_segments) and device: calls of one shape must be queued on one
-    stream at a time."""
-    pred_seg = _pq_planes(pred_seg, 'pred_seg', _SEG_KINDS)
-    pred_cls = _pq_planes(pred_cls, 'pred_cls', _PRED_KINDS)
-    gt_seg = _pq_planes(gt_seg, 'gt_seg', _SEG_KINDS)
-    gt_cls = _pq_planes(gt_cls, 'gt_cls', _PRED_KINDS)
+    synchronisation."""
+    pred_seg = _planes('panoptic_match', 'pred_seg', pred_seg, _SEG_KINDS, 'planes')
+    pred_cls = _planes('panoptic_match', 'pred_cls', pred_cls, _PRED_KINDS, 'planes')
+    gt_seg = _planes('panoptic_match', 'gt_seg', gt_seg, _SEG_KINDS, 'planes')
+    gt_cls = _planes('panoptic_match', 'gt_cls', gt_cls, _PRED_KINDS, 'planes')
     B, H, W = pred_seg.shape
     for what, t in (('pred_cls', pred_cls), ('gt_seg', gt_seg), ('gt_cls', gt_cls)):
         if tuple(t.shape) != (B, H, W) or t.device != pred_seg.device:
             raise ValueError('panoptic_match: pred_seg %s and %s %s differ' % (tuple(pred_seg.shape), what, tuple(t.shape)))
     if mask is not None:
-        mask = _pq_planes(mask, 'mask', (torch.float32,))
+        mask = _planes('panoptic_match', 'mask', mask, (torch.float32,), 'planes')
         if tuple(mask.shape) != (B, H, W) or mask.device != pred_seg.device:
             raise ValueError('panoptic_match: mask %s does not fit pred_seg %s' % (tuple(mask.shape), (B, H, W)))
     n_class, max_segments, ignore = int(n_class), int(max_segments), int(ignore)
@@ -3613,11 +3554,6 @@ def panoptic_match(pred_seg, pred_cls, gt_seg, gt_cls, n_class, *, mask=None, ig
                          '(at most 65535)' % (ignore, H, W, B))
     dev = pred_seg.device
     with torch.cuda.device(dev):
-        key = (B, max_segments, torch.cuda.current_device())
-        ws = _PQ_WS.get(key)
-        if ws is None:
-            nws = int(lib.him_panoptic_match_workspace(B, max_segments))
-            ws = _PQ_WS[key] = torch.empty((nws + 15) // 16 * 2, dtype=torch.int64, device=dev)
         if out is None:
             counts = torch.empty((n_class, 3), dtype=torch.int64, device=dev)
             iou_sum = torch.empty(n_class, dtype=torch.float64, device=dev)
@@ -3631,24 +3567,16 @@ def panoptic_match(pred_seg, pred_cls, gt_seg, gt_cls, n_class, *, mask=None, ig
                 raise ValueError('panoptic_match: out must be the (counts (%d, 3) int64, iou_sum (%d,) float64, status '
                                  '(%d, 4) int32) triple of an earlier call' % (n_class, n_class, B))
         matches = torch.empty((B, max_segments, 6), dtype=torch.int32, device=dev) if want_matches else None
-        lib.him_panoptic_match(_p(pred_seg), _SEG_KINDS[pred_seg.dtype], _p(pred_cls), _PRED_KINDS[pred_cls.dtype],
-                               _p(gt_seg), _SEG_KINDS[gt_seg.dtype], _p(gt_cls), _PRED_KINDS[gt_cls.dtype], _p(mask), B, H, W,
-                               n_class, ignore, max_segments, 0 if out is None else 1, _p(counts), _p(iou_sum), _p(matches),
-                               _p(status), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('panoptic_match', lib.him_panoptic_match_workspace(B, max_segments)) as ws:
+            lib.him_panoptic_match(_p(pred_seg), _SEG_KINDS[pred_seg.dtype], _p(pred_cls), _PRED_KINDS[pred_cls.dtype],
+                                   _p(gt_seg), _SEG_KINDS[gt_seg.dtype], _p(gt_cls), _PRED_KINDS[gt_cls.dtype], _p(mask), B,
+                                   H, W, n_class, ignore, max_segments, 0 if out is None else 1, _p(counts), _p(iou_sum),
+                                   _p(matches), _p(status), _p(ws), ws.numel(), _stream())
     return counts, iou_sum, status, matches
 
 
 # -- set-level metrics: Laplacian pyramid, segmented sort, sliced Wasserstein distance (include/him.h "Set-level metrics")
 SWD_PATCH, SORT_LDS_MAX, SWD_ZERO_DEVIATION = 7, 8192, 1
-_SWD_WS = {}            # (tag, shape..., device index) -> cached workspace; one stream at a time per shape
-
-
-def _swd_ws(key, nbytes, device):
-    key = key + (torch.cuda.current_device(),)
-    ws = _SWD_WS.get(key)
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = _SWD_WS[key] = torch.empty(max((int(nbytes) + 7) // 8, 2), dtype=torch.float64, device=device)
-    return ws
 
 
 def _swd_f32(t, what, dim):
@@ -3680,10 +3608,10 @@ def lap_pyramid(x, levels=None, want_gauss=False):
                          'divisible by 2^(levels - 1)' % (tuple(x.shape),))
     off = [int(lib.him_lap_level_offset(B, C, H, W, l)) for l in range(L + 1)]
     with torch.cuda.device(x.device):
-        ws = _swd_ws(('lap', B, C, H, W, L), need, x.device)
         lap = torch.empty(off[L], dtype=torch.float32, device=x.device)
         gauss = torch.empty(max(off[L] - off[1], 1), dtype=torch.float32, device=x.device) if want_gauss else None
-        lib.him_lap_pyramid(_p(x), B, C, H, W, L, _p(lap), _p(gauss), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('lap_pyramid', need) as ws:
+            lib.him_lap_pyramid(_p(x), B, C, H, W, L, _p(lap), _p(gauss), _p(ws), ws.numel(), _stream())
     laps = [lap[off[l]:off[l + 1]].view(B, C, H >> l, W >> l) for l in range(L)]
     if not want_gauss:
         return laps
@@ -3714,10 +3642,9 @@ def swd_gather(level, pos, desc, row0, stats, status):
         raise ValueError('swd_gather: stats must be (C, 4) float64 and status int32, both on the device')
     pos = pos.contiguous()
     with torch.cuda.device(level.device):
-        need = int(lib.him_swd_gather_ws(B, C))
-        ws = _swd_ws(('gather', B, C), need, level.device)
-        lib.him_swd_gather(_p(level), B, C, h, w, _p(pos), n, _p(desc), desc.shape[0], int(row0), _p(stats), _p(status),
-                           _p(ws), ws.numel() * 8, _stream())
+        with _scratch('swd_gather', lib.him_swd_gather_ws(B, C)) as ws:
+            lib.him_swd_gather(_p(level), B, C, h, w, _p(pos), n, _p(desc), desc.shape[0], int(row0), _p(stats), _p(status),
+                               _p(ws), ws.numel(), _stream())
     return int(row0) + B * n
 
 
@@ -3740,8 +3667,8 @@ def swd_project(desc, stats, dirs, status=None):
 def sort_segments(keys):
     """Sorts every row of the (S, N) (or (N,)) fp32 device tensor ``keys`` in place, ascending in the order of the
     sign-fixed bit pattern (-0 before +0, +inf before NaN); returns ``(keys, status)`` with the int32 ``status[0]`` the
-    number of NaNs.  Rows of up to SORT_LDS_MAX keys are sorted in LDS, longer ones by merge passes through a cached
-    workspace of the size of ``keys``.  Exact, identical bits from run to run.  Current stream, no host synchronisation."""
+    number of NaNs.  Rows of up to SORT_LDS_MAX keys are sorted in LDS, longer ones by merge passes through the cached
+    workspace, at least of the size of ``keys``.  Exact, identical bits from run to run.  Current stream, no host synchronisation."""
     if not torch.is_tensor(keys) or not keys.is_cuda:
         raise ValueError('sort_segments: keys must be a device tensor')
     if keys.dtype != torch.float32 or keys.dim() not in (1, 2) or not keys.is_contiguous() or keys.numel() == 0:
@@ -3750,10 +3677,9 @@ def sort_segments(keys):
     if S * N > 2 ** 31 - 1:
         raise ValueError('sort_segments: %d x %d keys, at most 2^31 - 1 per call' % (S, N))
     with torch.cuda.device(keys.device):
-        need = int(lib.him_sort_segments_ws(S, N))
-        ws = _swd_ws(('sort',), need, keys.device)
         status = torch.empty(1, dtype=torch.int32, device=keys.device)
-        lib.him_sort_segments(_p(keys), S, N, _p(status), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('sort_segments', lib.him_sort_segments_ws(S, N)) as ws:
+            lib.him_sort_segments(_p(keys), S, N, _p(status), _p(ws), ws.numel(), _stream())
     return keys, status
 
 
@@ -3831,9 +3757,8 @@ def feat_moments(feat, row0, n, sum, second):
                 or t.device != feat.device:
             raise ValueError('feat_moments: %s must be a contiguous %s float64 tensor on the device of feat' % (what, shape))
     with torch.cuda.device(feat.device):
-        need = int(lib.him_feat_moments_ws(n, D))
-        ws = _swd_ws(('moments',), need, feat.device)
-        lib.him_feat_moments(_p(feat), row0, n, D, _p(sum), _p(second), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('feat_moments', lib.him_feat_moments_ws(n, D)) as ws:
+            lib.him_feat_moments(_p(feat), row0, n, D, _p(sum), _p(second), _p(ws), ws.numel(), _stream())
     return sum, second
 
 
@@ -3860,14 +3785,14 @@ def kid_sums(x, y, ix, iy, gamma=0.0, coef0=1.0, status=None):
         if need == 0 or not 0.0 <= gamma < float('inf') or coef0 != coef0 or abs(coef0) == float('inf'):
             raise ValueError('kid_sums: n_subsets %d (1..65535), m %d (2..65536), gamma %r (>= 0), coef0 %r (finite)'
                              % (n_subsets, m, gamma, coef0))
-        ws = _swd_ws(('kid', n_subsets, m), need, x.device)
         out = torch.empty((n_subsets, 3), dtype=torch.float64, device=x.device)
         if status is None:
             status = torch.zeros(1, dtype=torch.int32, device=x.device)
         elif not torch.is_tensor(status) or status.dtype != torch.int32 or not status.is_cuda:
             raise ValueError('kid_sums: status must be an int32 device tensor')
-        lib.him_kid_sums(_p(x), x.shape[0], _p(y), y.shape[0], x.shape[1], _p(ix), _p(iy), n_subsets, m, gamma, coef0,
-                         _p(out), _p(status), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('kid_sums', need) as ws:
+            lib.him_kid_sums(_p(x), x.shape[0], _p(y), y.shape[0], x.shape[1], _p(ix), _p(iy), n_subsets, m, gamma, coef0,
+                             _p(out), _p(status), _p(ws), ws.numel(), _stream())
     return out, status
 
 
@@ -3889,7 +3814,7 @@ def knn_radii(x, k, status=None):
     distance 0).  Gram form with exact products on the fp64 matrix instruction; the matrix of pairs is never stored;
     identical bits from run to run.  A row with a non-finite feature sets KNN_NONFINITE in the int32 ``status[0]``, has
     the radius NaN and is nobody's neighbour.  ``1 <= k <= KNN_MAX_K``, ``k < n``, ``D <= FEAT_MAX_DIM``.  Current
-    stream, no host synchronisation, no autograd; the workspace is cached per shape and device."""
+    stream, no host synchronisation, no autograd."""
     x = _feat_matrix(x, 'knn_radii: x')
     n, D, k = x.shape[0], x.shape[1], int(k)
     if k < 1 or k > KNN_MAX_K or n <= k or D > FEAT_MAX_DIM:
@@ -3897,10 +3822,9 @@ def knn_radii(x, k, status=None):
                          % (k, KNN_MAX_K, tuple(x.shape), FEAT_MAX_DIM))
     status = _knn_status(status, x.device, 'knn_radii')
     with torch.cuda.device(x.device):
-        need = int(lib.him_knn_radii_ws(n, D, k))
-        ws = _swd_ws(('knn_radii', n, k), need, x.device)
         radii2 = torch.empty(n, dtype=torch.float64, device=x.device)
-        lib.him_knn_radii(_p(x), n, D, k, _p(radii2), _p(status), _p(ws), ws.numel() * 8, _stream())
+        with _scratch('knn_radii', lib.him_knn_radii_ws(n, D, k)) as ws:
+            lib.him_knn_radii(_p(x), n, D, k, _p(radii2), _p(status), _p(ws), ws.numel(), _stream())
     return radii2, status
 
 
@@ -3922,10 +3846,9 @@ def knn_membership(q, ref, radii2, want_cols=True, status=None):
         raise ValueError('knn_membership: radii2 must be a contiguous (%d,) float64 tensor on the device of q' % nr)
     status = _knn_status(status, q.device, 'knn_membership')
     with torch.cuda.device(q.device):
-        need = int(lib.him_knn_membership_ws(nq, nr, D))
-        ws = _swd_ws(('knn_member', nq, nr), need, q.device)
         row_count = torch.empty(nq, dtype=torch.int32, device=q.device)
         col_count = torch.empty(nr, dtype=torch.int32, device=q.device) if want_cols else None
-        lib.him_knn_membership(_p(q), nq, _p(ref), nr, D, _p(radii2.detach()), _p(row_count), _p(col_count), _p(status),
-                               _p(ws), ws.numel() * 8, _stream())
+        with _scratch('knn_membership', lib.him_knn_membership_ws(nq, nr, D)) as ws:
+            lib.him_knn_membership(_p(q), nq, _p(ref), nr, D, _p(radii2.detach()), _p(row_count), _p(col_count),
+                                   _p(status), _p(ws), ws.numel(), _stream())
     return row_count, col_count, status

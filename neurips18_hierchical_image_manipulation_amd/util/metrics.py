@@ -6,8 +6,8 @@ reference ships no metric code; the definitions are those of include/him.h "Eval
 and boundary metrics" and "Panoptic matching".  Every function queues device work on the current stream
 and returns device tensors; nothing synchronises with the host before ``Evaluator.summary()`` as long as every argument
 is a device tensor: a ``box`` given as a list or array (and any host tensor) is copied to the device first, which waits
-on the host.  The device calls share one cached workspace per shape and device (``ops.image_metrics`` /
-``ops.confusion``): calls of one shape must be queued on one stream at a time."""
+on the host.  The device calls of one operator share one cached workspace per device (``ops.image_metrics`` /
+``ops.confusion``); a call on another stream than the last one waits for that one's event first."""
 import json
 import math
 from collections import OrderedDict

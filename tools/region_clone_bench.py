@@ -111,7 +111,7 @@ def main():
         src_box, dst_box = (100, 200, 100 + W, 200 + H), (x0, y0, x0 + W, y0 + H)
         P = ops.canvas_crop_bicubic(src, src_box, H, W, normalize=False)
         u, status, resid = ops.region_poisson_solve(photo, x0, y0, P, window)
-        ws = ops._REGION_POISSON_WS[(H, W, photo.device.index)]
+        ws = ops._SCRATCH['region_poisson_solve', photo.device.index].buf
         stat = status.tolist()
         iters, cap = stat[3], 6 * (H + W)
         work = photo.clone()
@@ -119,7 +119,7 @@ def main():
         def solve(max_iter):
             lib.him_region_poisson_solve(photo.data_ptr(), HC, WC, x0, y0, H, W, P.data_ptr(), window.data_ptr(), 0, 1e-7,
                                          max_iter, u.data_ptr(), status.data_ptr(), resid.data_ptr(), ws.data_ptr(),
-                                         ws.numel() * 8, st)
+                                         ws.numel(), st)
 
         def apply():
             lib.him_region_poisson_apply(P.data_ptr(), u.data_ptr(), window.data_ptr(), work.data_ptr(), HC, WC, x0, y0, H,

@@ -51,7 +51,7 @@ def main():
         (Vy, Vyt, lamy), (Vx, Vxt, lamx) = ops.membrane_basis(ny, t, b), ops.membrane_basis(nx, l, r)
         scratch = [torch.empty_like(v) for v in (Vy, Vyt, lamy, Vx, Vxt, lamx)]
         m, status = ops.membrane_solve(photo, x0, y0, P)
-        ws = ops._MEMBRANE_WS[(H, W, l | r << 1 | t << 2 | b << 3, torch.cuda.current_device())]
+        ws = ops._SCRATCH['membrane_solve', torch.cuda.current_device()].buf
         work = photo.clone()
         matte = torch.empty((H, W), dtype=torch.float32, device=photo.device)
 
