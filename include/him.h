@@ -1229,6 +1229,53 @@ int him_layout_place(const void* inst_src, int inst_kind, int Hs, int Ws, int id
                      unsigned char* changed, int* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Affine layout edits (the reference ships none): rotate, mirror, shear or scale an instance and the pixels that go with
+ * it.  One geometric primitive, an inverse-mapped affine resampling -- NEAREST for ids, BICUBIC for pixels -- in front of
+ * the unchanged machinery of "Layout edits" and "Region Poisson clone".  Everything on `stream`, no host
+ * synchronisation, no workspace, results bit-identical from run to run.
+ *
+ * The map.  Pixel index i has its centre at coordinate i.  `inv` points to six int64 coefficients on the HOST (copied
+ * into the kernel arguments by the call; no device table, no upload), [a00, a01, a02, a10, a11, a12], the INVERSE map in
+ * units of 2^-24 source pixel: for the destination canvas indices (x, y)
+ *       U = a00 x + a01 y + a02        V = a10 x + a11 y + a12
+ *   nearest source pixel: xs = (U + 2^23) >> 24, ys = (V + 2^23) >> 24, arithmetic shifts (floor): the only tie rule.
+ *   bicubic: ix = U >> 24, tx = (U & (2^24 - 1)) 2^-24 (exact), iy / ty from V alike; taps ix - 1 .. ix + 2 by
+ *     iy - 1 .. iy + 2, indices clamped to the source plane (edge replicate); weights: Keys' kernel, a = -0.5, at the
+ *     distances 1 + t, t, 1 - t, 2 - t.  Point sampling, no prefilter: below scale 1 it aliases (the callers bound the
+ *     minification).  A zero fraction gives the weights (0, 1, 0, 0) exactly.
+ *   Limits: |a00|, |a01|, |a10|, |a11| <= 2^30 (a coefficient of 64), |a02|, |a12| <= 2^52.  Destination coordinates lie
+ *     inside +-(2^20 + 2^14), so each product stays below 2^51 and no sum leaves int64 (|U|, |V| < 2^53).  All
+ *     geometry is integer arithmetic: a 64-bit integer restatement gives the device's bits.
+ *
+ * him_layout_place_affine: him_layout_place with the tables xs / ys replaced by `inv`.  For every pixel (x, y) of the
+ *   destination box [dx0, dy0, dx1, dy1) inside the canvas the resampled mask is set iff sx0 <= xs < sx1 and
+ *   sy0 <= ys < sy1 and inst_src[ys, xs] == id (anything outside the source box reads as unset).  Everything else is
+ *   him_layout_place's contract: protect and the blocked count, label_dst = cls, inst_dst = new_id, changed = 1, the
+ *   six-int status, the four plane kinds, the refusals (with a NULL or 8-byte-misaligned inv and a coefficient beyond
+ *   the limits in the place of the tables'), the kernel layout, integer atomics behind wave reductions only.
+ *
+ * him_canvas_warp_affine: P[c, y, x] (3,H,W) fp32 = the bicubic sample above of src (3,Hs,Ws) fp32 at the destination
+ *   pixel (x0 + x, y0 + y).  Values are used as they are: no 8-bit round trip, no clamp to [0,1] (the overshoot of the
+ *   cubic stays; him_region_poisson_apply clamps at the end).  Non-finite source values are not special-cased: they
+ *   propagate through the taps that read them, a tap of weight 0 included.  Weights and sums in fp64 (48 multiply-adds
+ *   per pixel), narrowed to fp32 once per output.  On a map with zero fractions the result is the source value bit for
+ *   bit, with one exception: the sum starts from +0, so a source -0.0 comes out as +0.0.
+ *   HIM_E_INVALID before any launch: source sides outside 1..16384, H or W outside 1..2048 (the window
+ *   him_region_poisson_solve accepts), |x0| or |y0| > 2^20, a NULL or misaligned src / inv / P, P overlapping src, a
+ *   coefficient beyond the limits.
+ *   Kernel layout: a 256-thread workgroup per tile of 64 columns x 4 rows of the window, lane = column, the three
+ *   channels in one thread, taps gathered straight from global memory, plain stores; no atomics.
+ * ------------------------------------------------------------------------------------------- */
+#define HIM_AFFINE_FRAC_BITS 24
+#define HIM_AFFINE_MAX_WINDOW 2048
+int him_layout_place_affine(const void* inst_src, int inst_kind, int Hs, int Ws, int id, int sx0, int sy0, int sx1, int sy1,
+                            const long long* inv, void* label_dst, int label_kind, void* inst_dst, int Hd, int Wd, int dx0,
+                            int dy0, int dx1, int dy1, int cls, int new_id, const unsigned int* protect, int n_class,
+                            unsigned char* changed, int* status, void* stream);
+int him_canvas_warp_affine(const float* src, int Hs, int Ws, const long long* inv, int x0, int y0, int H, int W, float* P,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Set-level metrics (the reference ships none): the sliced Wasserstein distance between the Laplacian-pyramid patches of
  * two SETS of images (Karras et al., "Progressive Growing of GANs", ICLR 2018, section 5 and its sliced_wasserstein.py).
  * No network, no weights; everything on `stream`, no host synchronisation, no allocation, results bit-identical from

@@ -179,6 +179,9 @@ _SIGS = {
     'him_layout_erase': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P, P, P, c_size_t, P]),
     'him_layout_place': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P] +
                                 [c_int] * 8 + [P, c_int, P, P, P]),
+    'him_layout_place_affine': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P] +
+                                       [c_int] * 8 + [P, c_int, P, P, P]),
+    'him_canvas_warp_affine': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P]),
     'him_lap_levels': (C.c_uint, [c_int, c_int, c_int]),
     'him_lap_level_offset': (C.c_longlong, [c_int] * 5),
     'him_lap_pyramid_ws': (c_size_t, [c_int] * 5),

@@ -184,7 +184,6 @@ class JointInference(object):
         pixels ``layout_place`` wrote, the canvas after the first repaint being the boundary data
         (``ops.canvas_clone_region``; ``mixed``: per neighbour pair the stronger of the two gradients).  The
         pass's entry of ``report['passes']`` is then ``{'clone': status as host ints, 'resid': [...]}``."""
-        from ..preprocess import inst_info
         try:
             dx0, dy0, dx1, dy1 = (int(v) for v in dst_box)
         except (TypeError, ValueError):
@@ -193,20 +192,37 @@ class JointInference(object):
             raise ValueError('move_object: dst_box %r is empty' % (dst_box,))
         _seamless_flag(seamless)
         _clone_flags(keep_appearance, mixed)
+        dst_excl = (dx0, dy0, dx1 + 1, dy1 + 1)                       # exclusive, as the ops take boxes
+
+        def src_excl(box):
+            return box[0], box[1], box[2] + 1, box[3] + 1
+
+        def place(label_e, inst_e, obj_id, box, cls):
+            return ops.layout_place(label_e, inst_e, inst_original, obj_id, src_excl(box), dst_excl, cls,
+                                    obj_id if new_id is None else new_id, protect=protect)
+
+        def clone(box, img_canvas, placed):
+            return ops.canvas_clone_region(img_original, src_excl(box), img_canvas, dst_excl, placed, mixed=mixed)
+
+        return self._replace(obj, label_original, inst_original, img_original, opt, place, clone, fill, things, feather,
+                             reach, profile, seamless, keep_appearance)
+
+    def _replace(self, obj, label_original, inst_original, img_original, opt, place_fn, clone_fn, fill, things, feather,
+                 reach, profile, seamless, keep_appearance):
+        """What ``move_object`` and ``transform_object`` share: the erase, ``place_fn(label_e, inst_e, id, box, cls)`` (a
+        ``layout_place``), the box table, the repaint over the vacated box, then ``clone_fn(box, canvas, placed)`` (a
+        ``canvas_clone_region``) or the repaint over the box of the pixels written."""
+        from ..preprocess import inst_info
         obj_id, box, cls, label_e, inst_e, erase = self._erase(obj, label_original, inst_original, img_original, fill,
                                                                things, feather, reach, profile)
-        label_canvas, inst_canvas, placed, status = ops.layout_place(
-            label_e, inst_e, inst_original, obj_id, (box[0], box[1], box[2] + 1, box[3] + 1), (dx0, dy0, dx1 + 1, dy1 + 1),
-            cls, obj_id if new_id is None else new_id, protect=protect)
+        label_canvas, inst_canvas, placed, status = place_fn(label_e, inst_e, obj_id, box, cls)
         place = [int(v) for v in status.cpu().tolist()]
         info = inst_info(inst_canvas, label_canvas)
         img_canvas, first = self._repaint(box, cls, img_original, label_original, label_canvas, opt, feather, reach, profile,
                                           seamless)
         passes = [first]
         if place[0] > 0 and keep_appearance:
-            img_canvas, clone, resid = ops.canvas_clone_region(
-                img_original, (box[0], box[1], box[2] + 1, box[3] + 1), img_canvas, (dx0, dy0, dx1 + 1, dy1 + 1), placed,
-                mixed=mixed)
+            img_canvas, clone, resid = clone_fn(box, img_canvas, placed)
             passes.append({'clone': [int(v) for v in clone.cpu().tolist()], 'resid': [float(v) for v in resid.cpu().tolist()]})
         elif place[0] > 0:
             img_canvas, second = self._repaint(place[2:6], cls, img_canvas, label_original, label_canvas, opt, feather,
@@ -219,6 +235,42 @@ class JointInference(object):
         _, box, _ = edit_object(obj)
         return self.move_object(obj, scaled_box(box, scale), label_original, inst_original, img_original, opt,
                                 seamless=seamless, **kw)
+
+    def transform_object(self, obj, label_original, inst_original, img_original, opt, *, angle=0.0, scale=1.0, shear=0.0,
+                         flip='', shift=(0, 0), fill=None, things=None, protect=(), new_id=None, feather=None, reach=0,
+                         profile='smooth', seamless=False, keep_appearance=False, mixed=False):
+        """Turn, mirror, shear or scale ``obj`` about the centre of its box and move that centre by ``shift``
+        (``ops.affine_map``'s parameters and conventions: ``angle`` in degrees, counter-clockwise on the picture; below
+        scale 1 the sampling aliases).  ``move_object``'s sequence with the affine place and the affine clone in the
+        place of the separable ones: the erase on the originals, the object's original mask written
+        through the map (``ops.layout_place_affine``), the box table, the repaint over the vacated box, then the repaint
+        over the box of the pixels written or, with ``keep_appearance``, the object's own pixels warped bicubically
+        through the same map and Poisson-cloned onto the pixels written (``ops.canvas_clone_region_affine``).
+        -> as ``move_object``; ``report`` gains ``'affine': {'inv': [...], 'dst_box': [...]}``."""
+        _seamless_flag(seamless)
+        _clone_flags(keep_appearance, mixed)
+        _, box, _ = edit_object(obj)
+        amap = ops.affine_map((box[0], box[1], box[2] + 1, box[3] + 1), angle=angle, scale=scale, shear=shear, flip=flip,
+                              shift=shift)
+        def place(label_e, inst_e, obj_id, box, cls):
+            return ops.layout_place_affine(label_e, inst_e, inst_original, obj_id, amap, cls,
+                                           obj_id if new_id is None else new_id, protect=protect)
+
+        def clone(box, img_canvas, placed):
+            return ops.canvas_clone_region_affine(img_original, amap, img_canvas, placed, mixed=mixed)
+
+        result = self._replace(obj, label_original, inst_original, img_original, opt, place, clone, fill, things, feather,
+                               reach, profile, seamless, keep_appearance)
+        result[4]['affine'] = {'inv': list(amap.inv), 'dst_box': list(amap.dst_box)}
+        return result
+
+    def rotate_object(self, obj, angle, label_original, inst_original, img_original, opt, **kw):
+        """``transform_object`` with ``angle`` (degrees, counter-clockwise on the picture)."""
+        return self.transform_object(obj, label_original, inst_original, img_original, opt, angle=angle, **kw)
+
+    def flip_object(self, obj, axis, label_original, inst_original, img_original, opt, **kw):
+        """``transform_object`` with ``flip=axis``: ``'x'`` mirrors left-right, ``'y'`` top-bottom, ``'xy'`` both."""
+        return self.transform_object(obj, label_original, inst_original, img_original, opt, flip=axis, **kw)
 
 
 def _clone_flags(keep_appearance, mixed):

@@ -9,6 +9,7 @@ Weight gradients: parameters that live in a flat gradient arena (``optim.FlatAre
 of the arena, zeroed by ``zero_grad``) and autograd receives ``None`` -- no per-parameter add pass and no
 bucket copies for the RCCL all-reduce.
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -2665,25 +2666,41 @@ def canvas_clone_region(src, src_box, canvas, dst_box, region, *, mixed=False, r
     what = 'canvas_clone_region'
     sx0, sy0, sx1, sy1 = _layout_box(src_box, what + ': src_box')
     dx0, dy0, dx1, dy1 = _layout_box(dst_box, what + ': dst_box')
-    Hc, Wc, Hs, Ws = (int(v) for v in (canvas.shape[-2], canvas.shape[-1], src.shape[-2], src.shape[-1]))
+    Hs, Ws = int(src.shape[-2]), int(src.shape[-1])
     if sx0 < 0 or sy0 < 0 or sx1 > Ws or sy1 > Hs:
         raise ValueError('%s: src_box [%d, %d, %d, %d) is not inside the %d x %d source' % (what, sx0, sy0, sx1, sy1, Ws, Hs))
+    cx0, cy0, cx1, cy1 = _clone_window(what, src, canvas, (dx0, dy0, dx1, dy1), region, mixed, rtol, max_iter)
+    P = canvas_crop_bicubic(src, (sx0, sy0, sx1, sy1), dy1 - dy0, dx1 - dx0, normalize=False)
+    P = P[:, :, cy0 - dy0:cy1 - dy0, cx0 - dx0:cx1 - dx0].contiguous()
+    return _clone_patch(P, canvas, (cx0, cy0, cx1, cy1), region, mixed, rtol, max_iter)
+
+
+def _clone_window(what, src, canvas, dst_box, region, mixed, rtol, max_iter):
+    """``dst_box`` cut to the canvas -> ``(cx0, cy0, cx1, cy1)``, the window of a region clone, with the solve's options
+    and the tensors checked on the host."""
+    dx0, dy0, dx1, dy1 = dst_box
+    Hc, Wc = int(canvas.shape[-2]), int(canvas.shape[-1])
     cx0, cy0, cx1, cy1 = max(dx0, 0), max(dy0, 0), min(dx1, Wc), min(dy1, Hc)
     if cx1 <= cx0 or cy1 <= cy0:
         raise ValueError('%s: dst_box [%d, %d, %d, %d) does not meet the %d x %d canvas' % (what, dx0, dy0, dx1, dy1, Wc, Hc))
-    H, W = cy1 - cy0, cx1 - cx0
-    region_poisson_args(H, W, mixed, rtol, max_iter, what)
+    region_poisson_args(cy1 - cy0, cx1 - cx0, mixed, rtol, max_iter, what)
     if src.data_ptr() == canvas.data_ptr() or src.device != canvas.device:
         raise ValueError('%s: src and canvas are two tensors on one device' % what)
     _plane_geometry(canvas, what)
     if not torch.is_tensor(region) or not region.is_cuda or region.dtype != torch.uint8 or region.device != canvas.device \
             or tuple(region.shape) not in ((Hc, Wc), (1, Hc, Wc)):
         raise HimError('%s: region must be a uint8 (%d,%d) tensor on the canvas device' % (what, Hc, Wc))
-    P = canvas_crop_bicubic(src, (sx0, sy0, sx1, sy1), dy1 - dy0, dx1 - dx0, normalize=False)
-    P = P[:, :, cy0 - dy0:cy1 - dy0, cx0 - dx0:cx1 - dx0].contiguous()
-    window = region.reshape(Hc, Wc)[cy0:cy1, cx0:cx1].contiguous()
-    u, status, resid = region_poisson_solve(canvas, cx0, cy0, P, window, mixed=mixed, rtol=rtol, max_iter=max_iter)
-    region_poisson_apply(P, u, window, canvas, cx0, cy0)
+    return cx0, cy0, cx1, cy1
+
+
+def _clone_patch(P, canvas, window, region, mixed, rtol, max_iter):
+    """The patch ``P`` of the ``window`` Poisson-cloned into ``canvas`` on the window's pixels of the canvas-sized plane
+    ``region`` -> ``(canvas, status, resid)``."""
+    cx0, cy0, cx1, cy1 = window
+    Hc, Wc = int(canvas.shape[-2]), int(canvas.shape[-1])
+    part = region.reshape(Hc, Wc)[cy0:cy1, cx0:cx1].contiguous()
+    u, status, resid = region_poisson_solve(canvas, cx0, cy0, P, part, mixed=mixed, rtol=rtol, max_iter=max_iter)
+    region_poisson_apply(P, u, part, canvas, cx0, cy0)
     return canvas, status, resid
 
 
@@ -3290,6 +3307,33 @@ def layout_erase(label, inst, id=None, *, region=None, fill, n_class):
     return label_out.reshape(label.shape), inst_out.reshape(inst.shape), changed, status
 
 
+def _layout_place_args(what, label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_id, protect):
+    """The checked arguments of a place, separable or affine: ``(dst_box, id, src_box, cls, new_id, n_class, protect's
+    device table or None, label plane, instance plane, source plane)``; ValueError for anything refused."""
+    id = _layout_int(id, what + ': id', -2 ** 31, 2 ** 31 - 1)
+    sx0, sy0, sx1, sy1 = _layout_box(src_box, what + ': src_box')
+    dst_box = _layout_box(dst_box, what + ': dst_box')
+    _layout_int(cls, what + ': cls', -2 ** 31, 2 ** 31 - 1)
+    _layout_int(new_id, what + ': new_id', -2 ** 31, 2 ** 31 - 1)
+    prot = _layout_classes(protect, LAYOUT_MAX_CLASS, what + ': protect')
+    n_class = prot[-1] + 1 if prot else 1
+    lab = _planes(what + ': label_dst', 'src', label_dst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
+    ins = _planes(what + ': inst_dst', 'src', inst_dst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
+    src = _planes(what + ': inst_src', 'src', inst_src, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
+    if lab.shape != ins.shape or lab.device != ins.device or src.device != lab.device:
+        raise ValueError('%s: label_dst %s on %s, inst_dst %s on %s and inst_src on %s differ'
+                         % (what, tuple(lab.shape), lab.device, tuple(ins.shape), ins.device, src.device))
+    if src.dtype != ins.dtype:
+        raise ValueError('%s: inst_src is %s, inst_dst %s' % (what, src.dtype, ins.dtype))
+    Hs, Ws = src.shape
+    if sx0 < 0 or sy0 < 0 or sx1 > Ws or sy1 > Hs:
+        raise ValueError('%s: src_box [%d, %d, %d, %d) is not inside the %d x %d plane' % (what, sx0, sy0, sx1, sy1, Ws, Hs))
+    cls = _layout_int(cls, '%s: cls (%s plane)' % (what, lab.dtype), *_LAYOUT_ID_RANGE[lab.dtype])
+    new_id = _layout_int(new_id, '%s: new_id (%s plane)' % (what, ins.dtype), *_LAYOUT_ID_RANGE[ins.dtype])
+    table = _layout_table(prot, n_class, lab.device) if prot else None
+    return dst_box, id, (sx0, sy0, sx1, sy1), cls, new_id, n_class, table, lab, ins, src
+
+
 def layout_place(label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_id, *, protect=()):
     """Write the instance ``id`` of the plane ``inst_src``, cut out by ``src_box`` and resized to ``dst_box`` (both
     ``[xmin, ymin, xmax, ymax)``), onto copies of the pair ``label_dst`` / ``inst_dst``: ``(label_out, inst_out, changed,
@@ -3300,28 +3344,10 @@ def layout_place(label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_i
     xmax, ymax of the written pixels, inclusive as ``inst_summary``'s rows; (2^31 - 1, 2^31 - 1, -1, -1) when none].
     Planes as ``layout_erase`` takes them; ``inst_src`` has the dtype of ``inst_dst``.  Current stream, no host
     synchronisation, no autograd."""
-    id = _layout_int(id, 'layout_place: id', -2 ** 31, 2 ** 31 - 1)
-    sx0, sy0, sx1, sy1 = _layout_box(src_box, 'layout_place: src_box')
-    dx0, dy0, dx1, dy1 = _layout_box(dst_box, 'layout_place: dst_box')
-    _layout_int(cls, 'layout_place: cls', -2 ** 31, 2 ** 31 - 1)
-    _layout_int(new_id, 'layout_place: new_id', -2 ** 31, 2 ** 31 - 1)
-    prot = _layout_classes(protect, LAYOUT_MAX_CLASS, 'layout_place: protect')
-    n_class = prot[-1] + 1 if prot else 1
-    lab = _planes('layout_place: label_dst', 'src', label_dst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
-    ins = _planes('layout_place: inst_dst', 'src', inst_dst, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
-    src = _planes('layout_place: inst_src', 'src', inst_src, _PRED_KINDS, 'planes', max_side=_EDT_MAX_SIDE, single=True)
-    if lab.shape != ins.shape or lab.device != ins.device or src.device != lab.device:
-        raise ValueError('layout_place: label_dst %s on %s, inst_dst %s on %s and inst_src on %s differ'
-                         % (tuple(lab.shape), lab.device, tuple(ins.shape), ins.device, src.device))
-    if src.dtype != ins.dtype:
-        raise ValueError('layout_place: inst_src is %s, inst_dst %s' % (src.dtype, ins.dtype))
+    (dx0, dy0, dx1, dy1), id, (sx0, sy0, sx1, sy1), cls, new_id, n_class, table, lab, ins, src = _layout_place_args(
+        'layout_place', label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_id, protect)
     Hd, Wd = lab.shape
     Hs, Ws = src.shape
-    if sx0 < 0 or sy0 < 0 or sx1 > Ws or sy1 > Hs:
-        raise ValueError('layout_place: src_box [%d, %d, %d, %d) is not inside the %d x %d plane' % (sx0, sy0, sx1, sy1, Ws, Hs))
-    cls = _layout_int(cls, 'layout_place: cls (%s plane)' % lab.dtype, *_LAYOUT_ID_RANGE[lab.dtype])
-    new_id = _layout_int(new_id, 'layout_place: new_id (%s plane)' % ins.dtype, *_LAYOUT_ID_RANGE[ins.dtype])
-    table = _layout_table(prot, n_class, lab.device) if prot else None
     with torch.cuda.device(lab.device):
         xs = _layout_index(sx1 - sx0, dx1 - dx0, lab.device)
         ys = _layout_index(sy1 - sy0, dy1 - dy0, lab.device)
@@ -3332,6 +3358,190 @@ def layout_place(label_dst, inst_dst, inst_src, id, src_box, dst_box, cls, new_i
                              _p(label_out), _PRED_KINDS[lab.dtype], _p(inst_out), Hd, Wd, dx0, dy0, dx1, dy1, cls, new_id,
                              _p(table), n_class, _p(changed), _p(status), _stream())
     return label_out.reshape(label_dst.shape), inst_out.reshape(inst_dst.shape), changed, status
+
+
+# -- affine layout edits: include/him.h "Affine layout edits" ------------------------------------------------------------
+AFFINE_FRAC_BITS = 24
+AFFINE_MAX_LINEAR, AFFINE_MAX_OFFSET = 1 << 30, 1 << 52
+AffineMap = collections.namedtuple('AffineMap', ('inv', 'fwd', 'dst_box', 'src_box'))
+AffineMap.__doc__ = """An affine edit of a source box: ``inv``, the six ints [a00, a01, a02, a10, a11, a12] of the inverse
+map in units of 2^-24 source pixel as the device takes them; ``fwd``, the float64 2 x 3 forward map (read-only);
+``dst_box`` ``[xmin, ymin, xmax, ymax)``: the forward image of the source box's pixel squares, rounded outwards;
+``src_box`` as given."""
+
+
+def _affine_pair(v, what, scalar_ok=False):
+    import math
+    import numbers
+    if scalar_ok and isinstance(v, numbers.Real) and not isinstance(v, bool):
+        v = (v, v)
+    try:
+        a, b = v
+        if isinstance(a, bool) or isinstance(b, bool):
+            raise TypeError
+        a, b = float(a), float(b)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be %stwo numbers, got %r' % (what, 'a number or ' if scalar_ok else '', v))
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError('%s must be finite, got %r' % (what, v))
+    return a, b
+
+
+def affine_map(src_box, *, angle=0.0, scale=1.0, shear=0.0, flip='', shift=(0, 0), dst_center=None):
+    """The ``AffineMap`` that turns the pixels of ``src_box`` (``[xmin, ymin, xmax, ymax)``, as ``layout_place`` takes it)
+    about the box's centre: mirror (``flip``, a subset of ``'xy'``: ``'x'`` reverses the columns), scale (a number or
+    ``(sx, sy)``), shear (``shear``: the tangent of a horizontal shear, x += shear * y), then rotate by ``angle`` degrees
+    counter-clockwise as seen on the picture (y points down: ``Image.rotate``'s sense), and put the centre at
+    ``dst_center`` (None: the source box's centre) plus ``shift``.  Pixel index i has its centre at coordinate i.
+
+    When the linear part is a signed permutation matrix (quarter turns and flips, scale 1, shear 0) the centre is snapped
+    by at most half a pixel towards +x / +y so that pixel centres land on pixel centres: every fraction of the map is
+    zero, the nearest rule meets no tie and the bicubic weights are exactly (0, 1, 0, 0): the edit permutes pixels.
+
+    The device samples points: NEAREST for ids, the 4 x 4 Keys cubic for pixels, with no prefilter.  Below scale 1 this
+    aliases, because Pillow's resize widens its support there and this map does not; hence the bound on the minification.
+    ValueError: a non-finite parameter, a singular value of the linear part outside [1/4, 4], ``|shear| > 2``, a flip
+    that is no subset of ``'xy'``, a destination beyond the coordinates the device accepts."""
+    import fractions
+    import math
+    import numbers
+    import numpy as np
+    what = 'affine_map'
+    sx0, sy0, sx1, sy1 = _layout_box(src_box, what + ': src_box')
+    for name, v in (('angle', angle), ('shear', shear)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+            raise ValueError('%s: %s must be a finite number, got %r' % (what, name, v))
+    angle, shear = float(angle), float(shear)
+    kx, ky = _affine_pair(scale, what + ': scale', scalar_ok=True)
+    shx, shy = _affine_pair(shift, what + ': shift')
+    if abs(shear) > 2.0:
+        raise ValueError('%s: |shear| > 2, got %r' % (what, shear))
+    if not isinstance(flip, str) or len(set(flip)) != len(flip) or not set(flip) <= set('xy'):
+        raise ValueError("%s: flip must be a subset of 'xy', got %r" % (what, flip))
+    quarter = angle % 90.0 == 0.0
+    if quarter:
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(angle // 90.0) % 4]
+    else:
+        c, s = math.cos(math.radians(angle)), math.sin(math.radians(angle))
+    fx, fy = (-1.0 if 'x' in flip else 1.0), (-1.0 if 'y' in flip else 1.0)
+    L = np.array([[c, s], [-s, c]]) @ np.array([[1.0, shear], [0.0, 1.0]]) @ np.diag([kx * fx, ky * fy])
+    sv = np.linalg.svd(L, compute_uv=False)
+    if not (sv.max() <= 4.0 * (1 + 1e-12) and sv.min() >= 0.25 * (1 - 1e-12)):
+        raise ValueError('%s: the singular values %s of the linear part leave [1/4, 4]' % (what, sv.tolist()))
+    permutation = quarter and kx == 1.0 and ky == 1.0 and shear == 0.0
+    cs = np.array([(sx0 + sx1 - 1) / 2.0, (sy0 + sy1 - 1) / 2.0])
+    cd = (cs if dst_center is None else np.array(_affine_pair(dst_center, what + ': dst_center'))) + np.array([shx, shy])
+    if permutation:
+        L = np.rint(L)                                   # exact already; -0.0 -> a plain zero after the sums below
+        t = L @ cs
+        cd = t + np.floor(cd - t + 0.5)
+        Linv = L.T.copy()
+    else:
+        det = L[0, 0] * L[1, 1] - L[0, 1] * L[1, 0]
+        Linv = np.array([[L[1, 1], -L[0, 1]], [-L[1, 0], L[0, 0]]]) / det
+    off = cs - Linv @ cd
+    one = float(1 << AFFINE_FRAC_BITS)
+    inv = tuple(int(math.floor(float(v) * one + 0.5))
+                for v in (Linv[0, 0], Linv[0, 1], off[0], Linv[1, 0], Linv[1, 1], off[1]))
+    if max(abs(inv[k]) for k in (0, 1, 3, 4)) > AFFINE_MAX_LINEAR or max(abs(inv[2]), abs(inv[5])) > AFFINE_MAX_OFFSET:
+        raise ValueError('%s: the inverse map %s leaves the coefficients the device accepts' % (what, list(inv)))
+    fwd = np.concatenate([L, (cd - L @ cs)[:, None]], axis=1) + 0.0
+    fwd.setflags(write=False)
+    # the destination box from the integer map itself, in exact rationals: the corners of the source box's pixel squares
+    # (U in [sx0 - 1/2, sx1 - 1/2) in 2^-24 units) through the inverse of [a00 a01; a10 a11]
+    a00, a01, a02, a10, a11, a12 = inv
+    det = a00 * a11 - a01 * a10
+    half = 1 << (AFFINE_FRAC_BITS - 1)
+    xs, ys = [], []
+    for U in ((sx0 << AFFINE_FRAC_BITS) - half, (sx1 << AFFINE_FRAC_BITS) - half):
+        for V in ((sy0 << AFFINE_FRAC_BITS) - half, (sy1 << AFFINE_FRAC_BITS) - half):
+            xs.append(fractions.Fraction(a11 * (U - a02) - a01 * (V - a12), det))
+            ys.append(fractions.Fraction(a00 * (V - a12) - a10 * (U - a02), det))
+    dx0, dy0 = math.ceil(min(xs)), math.ceil(min(ys))
+    dx1, dy1 = max(math.floor(max(xs)) + 1, dx0 + 1), max(math.floor(max(ys)) + 1, dy0 + 1)
+    if min(dx0, dy0) < -LAYOUT_MAX_COORD or max(dx1, dy1) > LAYOUT_MAX_COORD:
+        raise ValueError('%s: dst_box [%d, %d, %d, %d) beyond +-2^20' % (what, dx0, dy0, dx1, dy1))
+    return AffineMap(inv, fwd, (dx0, dy0, dx1, dy1), (sx0, sy0, sx1, sy1))
+
+
+def _affine_inv(amap, what):
+    """The six coefficients of ``amap`` as a host int64 array for the C ABI (the call copies them)."""
+    if not isinstance(amap, AffineMap):
+        raise ValueError('%s: amap must be the AffineMap ops.affine_map returns, got %r' % (what, type(amap).__name__))
+    try:
+        n = len(amap.inv)
+    except TypeError:
+        n = -1
+    if n != 6:
+        raise ValueError('%s: amap.inv has six coefficients, got %r' % (what, amap.inv))
+    inv = tuple(_layout_int(v, what + ': amap.inv', -lim, lim)
+                for v, lim in zip(amap.inv, (AFFINE_MAX_LINEAR, AFFINE_MAX_LINEAR, AFFINE_MAX_OFFSET) * 2))
+    return (ctypes.c_longlong * 6)(*inv)
+
+
+def layout_place_affine(label_dst, inst_dst, inst_src, id, amap, cls, new_id, *, protect=()):
+    """``layout_place`` through the affine edit ``amap`` (``affine_map``): the instance ``id`` of the plane ``inst_src``
+    inside ``amap.src_box``, resampled NEAREST through the inverse map -- destination pixel (x, y) reads the source pixel
+    ``((U + 2^23) >> 24, (V + 2^23) >> 24)``, unset when that lies outside the source box -- onto copies of the pair
+    ``label_dst`` / ``inst_dst`` over ``amap.dst_box`` (clipped to the canvas).  Everything else, the four results
+    ``(label_out, inst_out, changed, status)`` included, as ``layout_place``.  Current stream, no host synchronisation,
+    no table upload, no autograd."""
+    what = 'layout_place_affine'
+    inv = _affine_inv(amap, what)
+    (dx0, dy0, dx1, dy1), id, (sx0, sy0, sx1, sy1), cls, new_id, n_class, table, lab, ins, src = _layout_place_args(
+        what, label_dst, inst_dst, inst_src, id, amap.src_box, amap.dst_box, cls, new_id, protect)
+    Hd, Wd = lab.shape
+    Hs, Ws = src.shape
+    with torch.cuda.device(lab.device):
+        label_out, inst_out = lab.clone(), ins.clone()
+        changed = torch.zeros((Hd, Wd), dtype=torch.uint8, device=lab.device)
+        status = torch.empty(6, dtype=torch.int32, device=lab.device)
+        lib.him_layout_place_affine(_p(src), _PRED_KINDS[src.dtype], Hs, Ws, id, sx0, sy0, sx1, sy1,
+                                    ctypes.addressof(inv), _p(label_out), _PRED_KINDS[lab.dtype], _p(inst_out), Hd, Wd,
+                                    dx0, dy0, dx1, dy1, cls, new_id, _p(table), n_class, _p(changed), _p(status), _stream())
+    return label_out.reshape(label_dst.shape), inst_out.reshape(inst_dst.shape), changed, status
+
+
+def _affine_window(window, what):
+    try:
+        x0, y0, H, W = window
+    except (TypeError, ValueError):
+        raise ValueError('%s: window must be (x0, y0, H, W), got %r' % (what, window))
+    x0, y0 = (_layout_int(v, what + ': window origin', -LAYOUT_MAX_COORD, LAYOUT_MAX_COORD) for v in (x0, y0))
+    H, W = (_layout_int(v, what + ': window size', 1, REGION_POISSON_MAX_N) for v in (H, W))
+    return x0, y0, H, W
+
+
+def canvas_warp_affine(src, amap, window):
+    """``P`` (1,3,H,W) fp32: the RGB planes ``src`` (1,3,Hs,Ws) seen through the affine edit ``amap`` on the ``window``
+    ``(x0, y0, H, W)`` of the destination canvas: ``P[0, c, y, x]`` is the bicubic sample (Keys, a = -0.5, 4 x 4 taps
+    clamped to the source plane, fp64 weights and sums narrowed once) of channel c at the source point the inverse map
+    gives for the destination pixel ``(x0 + x, y0 + y)``.  No 8-bit round trip and no clamp: the cubic's overshoot stays.
+    H, W in 1..2048.  Current stream, no host synchronisation, no autograd."""
+    what = 'canvas_warp_affine'
+    inv = _affine_inv(amap, what)
+    x0, y0, H, W = _affine_window(window, what)
+    C, Hs, Ws = _plane_geometry(src, what)
+    if C != 3 or max(Hs, Ws) > _EDT_MAX_SIDE:
+        raise HimError('%s: RGB planes with sides up to %d, got %s' % (what, _EDT_MAX_SIDE, tuple(src.shape)))
+    with torch.cuda.device(src.device):
+        P = torch.empty((1, 3, H, W), dtype=torch.float32, device=src.device)
+        lib.him_canvas_warp_affine(_p(src), Hs, Ws, ctypes.addressof(inv), x0, y0, H, W, _p(P), _stream())
+    return P
+
+
+def canvas_clone_region_affine(src, amap, canvas, region, *, mixed=False, rtol=1e-7, max_iter=None):
+    """``canvas_clone_region`` through the affine edit ``amap``: the patch is ``canvas_warp_affine(src, amap, window)``
+    with the window = ``amap.dst_box`` cut to the canvas, Poisson-cloned in place into ``canvas`` (1,3,Hc,Wc) on the
+    nonzero pixels of the canvas-sized uint8 plane ``region`` (``layout_place_affine``'s ``changed``) -> ``(canvas,
+    status, resid)``.  ``region_poisson_solve`` then ``region_poisson_apply``, unchanged; options are checked on the host
+    before any device work.  ``src`` must not alias ``canvas``.  Current stream, no host synchronisation."""
+    what = 'canvas_clone_region_affine'
+    _affine_inv(amap, what)
+    dst_box = _layout_box(amap.dst_box, what + ': amap.dst_box')
+    cx0, cy0, cx1, cy1 = _clone_window(what, src, canvas, dst_box, region, mixed, rtol, max_iter)
+    P = canvas_warp_affine(src, amap, (cx0, cy0, cy1 - cy0, cx1 - cx0))
+    return _clone_patch(P, canvas, (cx0, cy0, cx1, cy1), region, mixed, rtol, max_iter)
 
 
 # -- boundary-weighted and surface losses (include/him.h "Boundary-weighted and surface losses") ------------------------
